@@ -2,10 +2,19 @@
 """Benchmark: Mrays/s of the MI355X bounce loop on BASELINE.json configs[1].
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--accel bvh|grid|grid_fast]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds the scene,
+warms up, times the K steps and prints the result line.  ``--dump-outputs DIR``
+also writes what the last timed step left in the caller's hands (the
+accumulator image) as ``DIR/<name>.npy``.  Everything else this file measures
+runs only with ``--full``: the ``alt_mode``, the ``targets``, the ``full_run``
+renders, the one-pipeline roofline passes and the CPU baseline described below
+(each still has its own ``--no-...`` / empty-list switch).
 
 Default mode ``grid_fast`` returns the reference algorithm's results bit for
-bit (uniform-grid semantics computed through a BVH hit set); the exact
-closest-hit ``bvh`` mode is timed after it and reported under ``alt_mode``.
+bit (uniform-grid semantics computed through a BVH hit set); with ``--full`` the
+exact closest-hit ``bvh`` mode is timed after it and reported under ``alt_mode``.
 
 Workload (configs[1]): diffuse-only synthetic OBJ (~100k triangles, a
 displaced torus in an open-front room with emissive panels), 1280x1024,
@@ -69,12 +78,20 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=0,
                     help="GPUs (ranks); 0: WORLD_SIZE when a launcher set it, else 1.  N > 1 without a launcher: "
                          "bench.py starts the N ranks itself")
-    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=32, help="timed steps (one sample per pixel each)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the alt mode, the targets, the full-spp "
+                         "renders, the one-pipeline roofline passes and the CPU baseline (minutes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the accumulator image they produced to DIR/image.npy "
+                         "(float32; a fixed seeded pixel sample above 64 MB) and the per-bounce segment counts to "
+                         "DIR/segments_per_bounce.npy (float64)")
     ap.add_argument("--accel", choices=["bvh", "grid", "grid_fast"], default="grid_fast",
                     help="grid_fast: the reference's grid results (bit-identical), BVH-accelerated; "
                          "bvh: exact closest hit; grid: the reference's list-walking DDA")
-    ap.add_argument("--alt-accel", default="bvh", help="second mode timed after the main one ('' to skip)")
+    ap.add_argument("--alt-accel", default="bvh",
+                    help="with --full: second mode timed after the main one ('' to skip)")
     ap.add_argument("--ntri", type=int, default=100_000)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=1024)
@@ -85,7 +102,7 @@ def parse(argv=None):
     ap.add_argument("--scene", default="", help="a scene file instead of the synthetic OBJ scene (e.g. "
                                                 "scenes/reference_scene.txt); its RENDER block's bounces apply")
     ap.add_argument("--targets", default="target_1m,configs2,configs4",
-                    help="extra workloads timed after the main line ('' to skip): target_1m = north_star's "
+                    help="with --full: extra workloads timed after the main line ('' to skip): target_1m = north_star's "
                          "1M-triangle scene at 1280x1024; configs2 = the README scene at 2800x2240; configs4 = "
                          "the 10M-triangle scene at 1280x1024, 16 bounces")
     ap.add_argument("--target-steps", type=int, default=16)
@@ -102,7 +119,12 @@ def parse(argv=None):
     ap.add_argument("--hw-queues", type=int, default=16,
                     help="GPU_MAX_HW_QUEUES for this process (HIP default 4): one hardware queue per "
                          "pipeline stream (max 32)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: nothing but the headline figure's own steps
+        args.alt_accel, args.targets = "", ""
+        args.no_full_runs = args.no_profile = args.no_cpu_baseline = True
+    return args
 
 
 def spawn_ranks(n, argv):
@@ -303,7 +325,7 @@ def bound_fracs(obj, path="line"):
     return bad
 
 
-def timed_run(P, ctx, scene, cfg, K, W, iter_base, reduce_image, full_spp=0):
+def timed_run(P, ctx, scene, cfg, K, W, iter_base, reduce_image, full_spp=0, keep_image=False):
     """Warm up, then time exactly K iterations (this rank's [rank*K, (rank+1)*K))
     between barrier + synchronize pairs; the accumulator all-reduce (RCCL) is
     inside the timed region.  No profiling events in the timed region.  With
@@ -311,7 +333,9 @@ def timed_run(P, ctx, scene, cfg, K, W, iter_base, reduce_image, full_spp=0):
     over the ranks (the configuration's own sample count), timed the same way.
     Trace faults (waves that hit the iteration cap) of the warmup and of both
     timed regions make the run invalid.  Returns the max-over-ranks times, the
-    all-rank segment totals and the per-bounce counts of rank 0's K steps."""
+    all-rank segment totals and the per-bounce counts of rank 0's K steps; with
+    ``keep_image`` also a host copy of the accumulator as the K timed steps left
+    it (after the all-reduce), taken outside the timed region."""
     from pathtracerap_amd.dist import shard_iterations
     torch, dev, rank, world = ctx.torch, ctx.dev, ctx.rank, ctx.world
     image = torch.zeros(cfg.width * cfg.height * 3, dtype=torch.float32, device=dev)
@@ -348,6 +372,7 @@ def timed_run(P, ctx, scene, cfg, K, W, iter_base, reduce_image, full_spp=0):
     while per_bounce and per_bounce[-1] == 0:
         per_bounce.pop()
     img_ok = bool(torch.isfinite(image).all().item())
+    kept = image.cpu().numpy().reshape(cfg.height, cfg.width, 3).copy() if keep_image else None
     full = None
     if full_spp > 0:
         first, n = shard_iterations(full_spp, rank, world)
@@ -365,12 +390,37 @@ def timed_run(P, ctx, scene, cfg, K, W, iter_base, reduce_image, full_spp=0):
         raise SystemExit(f"bench: persistent-trace wave(s) hit the iteration cap on some rank "
                          f"(max {int(fmax)}); result invalid")
     res = dict(elapsed=el_max, seg=seg_total, seg_primary=seg0_total, per_bounce=per_bounce, img_ok=img_ok,
-               pipes=pipes, faults=int(fmax))
+               pipes=pipes, faults=int(fmax), image=kept)
     if full is not None:
         fel, = ctx.reduce([full[0]], "max")
         fseg, fseg0, fok = ctx.reduce(full[1:], "sum")
         res["full"] = dict(spp=full_spp, elapsed=fel, seg=fseg, seg_primary=fseg0, img_ok=fok == world)
     return res
+
+
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(out_dir, image, per_bounce, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: what the timed steps computed, one .npy per array.
+    ``image.npy``: the float32 accumulator (height, width, 3), the sum over the
+    timed steps' samples, as a caller of renderLoop reads it back.  Above
+    ``cap_bytes`` a fixed seeded sample of its pixels is written instead, as
+    (n, 3), with the flat pixel indices in ``image_sample_index.npy`` (float64).
+    ``segments_per_bounce.npy``: rank 0's per-bounce segment counts (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    counts = np.asarray(per_bounce, dtype=np.float64)
+    budget = cap_bytes - counts.nbytes
+    if image.nbytes > budget:
+        npix = image.shape[0] * image.shape[1]
+        n = max(1, budget // (3 * 4 + 8))                 # 12 B of pixel + 8 B of index each
+        idx = np.sort(np.random.RandomState(0).choice(npix, size=n, replace=False))
+        np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
+        image = image.reshape(npix, 3)[idx]
+    np.save(os.path.join(out_dir, "image.npy"), image)
+    np.save(os.path.join(out_dir, "segments_per_bounce.npy"), counts)
 
 
 def rates(res, K, npix, world):
@@ -552,8 +602,11 @@ def main():
     K, W = args.steps, args.warmup
     full_main = 0 if args.no_full_runs or not is_default_workload(args) else SPP["configs1"]
 
-    main_res = timed_run(P, ctx, scene, cfg, K, W, 1_000_000, reduce_image=True, full_spp=full_main)
+    main_res = timed_run(P, ctx, scene, cfg, K, W, 1_000_000, reduce_image=True, full_spp=full_main,
+                         keep_image=bool(args.dump_outputs) and rank == 0)
     per_bounce = main_res["per_bounce"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, main_res.pop("image"), per_bounce)
     workload_key = f"{args.accel}_{args.ntri}_{args.width}x{args.height}_b{args.bounces}" + \
         ("_metal" if args.metallic else "")
 
@@ -655,6 +708,7 @@ def main():
                 cpu = {"error": repr(e)}
         out = {
             "metric": METRIC, "value": r_main["value"], "unit": "Mrays/s", "n_gpus": world, "steps": K,
+            "full": args.full,
             "warmup": W, "ms_per_step": r_main["ms_per_step"], "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "samples_per_sec": r_main["samples_per_sec"],

@@ -6,7 +6,8 @@
 #
 #   tests[=EXPR]          pytest -m gpu (EXPR: a -k expression)
 #   vtests=NAME:EXPR      the same against build_variants/lib_NAME.so (PT_LIB_PATH)
-#   bench[=ARGS]          python bench.py ARGS (no ARGS: the driver's default line)
+#   bench[=ARGS]          python bench.py ARGS (no ARGS: the headline figure alone; --full: the whole line
+#                         with alt mode, targets, full-spp runs, roofline passes and CPU baseline)
 #   prof[=ARGS]           rocprofv3 --kernel-trace --stats of bench.py ARGS
 #   ktrace[=ARGS]         rocprofv3 --kernel-trace of bench.py ARGS + scripts/timeline.py
 #   pmc[=ARGS]            FETCH_SIZE and WRITE_SIZE, one --pmc pass each, of bench.py ARGS
@@ -18,7 +19,7 @@
 #   abbench=R@ARGS@N1,N2  R interleaved rounds of bench.py ARGS (main line only) over library builds
 #   py=SCRIPT ARGS        python SCRIPT ARGS (a measurement script under scripts/)
 #
-# Example: bash scripts/gpu_run.sh tests "bench=--steps 32" "prof=--pipelines 1 --targets= --no-cpu-baseline"
+# Example: bash scripts/gpu_run.sh tests "bench=--full --steps 32" "prof=--pipelines 1"
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp

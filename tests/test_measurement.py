@@ -231,3 +231,44 @@ def test_bench_nccl_needs_a_gpu_per_rank():
                    {"WORLD_SIZE": str(n + 1), "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",
                     "MASTER_PORT": "1"}, timeout=120)
     assert p.returncode != 0 and "one GPU per rank" in p.stderr
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full nothing beside the timed steps runs (no alt mode, targets,
+    full-spp renders, roofline passes or CPU baseline); --full leaves every one
+    of them at its default, and its own switches still turn them off."""
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full) == (7, 3, False)
+    assert a.alt_accel == "" and a.targets == ""
+    assert a.no_full_runs and a.no_profile and a.no_cpu_baseline
+    f = b.parse(["--full"])
+    assert f.full and f.alt_accel == "bvh" and f.targets == "target_1m,configs2,configs4"
+    assert not (f.no_full_runs or f.no_profile or f.no_cpu_baseline)
+    f = b.parse(["--full", "--targets=configs2", "--no-cpu-baseline"])
+    assert f.targets == "configs2" and f.no_cpu_baseline and not f.no_profile
+
+
+def test_bench_write_outputs(tmp_path):
+    """--dump-outputs: the whole float32 image when it fits the cap, else the same
+    seeded pixel sample every time, with its indices; never more than the cap."""
+    import numpy as np
+    b = _bench()
+    assert b.DUMP_CAP_BYTES == 64 * 2 ** 20
+    img = np.arange(7 * 5 * 3, dtype=np.float32).reshape(7, 5, 3)
+    d = str(tmp_path / "whole")
+    b.write_outputs(d, img, [35, 20, 4])
+    assert sorted(os.listdir(d)) == ["image.npy", "segments_per_bounce.npy"]
+    got = np.load(os.path.join(d, "image.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    seg = np.load(os.path.join(d, "segments_per_bounce.npy"))
+    assert seg.dtype == np.float64 and seg.tolist() == [35.0, 20.0, 4.0]
+    cap = 24 + 10 * 20                                   # the counts + room for 10 sampled pixels
+    d1, d2 = str(tmp_path / "s1"), str(tmp_path / "s2")
+    b.write_outputs(d1, img, [35, 20, 4], cap_bytes=cap)
+    b.write_outputs(d2, img, [35, 20, 4], cap_bytes=cap)
+    s1, i1 = np.load(os.path.join(d1, "image.npy")), np.load(os.path.join(d1, "image_sample_index.npy"))
+    assert s1.shape == (10, 3) and s1.dtype == np.float32 and i1.dtype == np.float64
+    assert len(set(i1.tolist())) == 10 and np.array_equal(s1, img.reshape(-1, 3)[i1.astype(np.int64)])
+    assert np.array_equal(i1, np.load(os.path.join(d2, "image_sample_index.npy")))
+    assert s1.nbytes + i1.nbytes + seg.nbytes <= cap
