@@ -63,7 +63,9 @@ typedef struct pt_render_config {
     double cam[3];            /* camera origin (Renderer.cpp:528), default (0,0,920) */
     double plane_z;           /* image plane z (Renderer.cpp:543), default 900 */
     double plane_x0, plane_y0, plane_w, plane_h;  /* Renderer.cpp:538-542: -10,-4,20,16 */
-    int block;                /* bounce-kernel workgroup = compaction chunk: 64 (default), 128 or 256 */
+    int block;                /* bounce-kernel workgroup = compaction chunk: 64 (default), 128 or 256;
+                                 any other value (0, 96, ...) falls back to 256.  Results are identical
+                                 for every value */
     int pipelines;            /* iterations in flight on their own HIP streams, 1..32 (default 16); results
                                  are identical for every value (contributions merge in iteration order).
                                  Loading the library sets GPU_MAX_HW_QUEUES=16 (one hardware queue per

@@ -292,6 +292,7 @@ int Scene::relayoutPairs(int n0, int root) {
 // 2^27 in the scene, gets no 4-wide BLAS (root -1): every BLAS path walks the
 // 4-wide nodes and there is no binary fallback, so Renderer::allocateOnGPU then
 // refuses the scene for them (grid mode, which needs no BLAS, still runs).
+// A mesh without triangles also has root -1, and is not refused: nothing can hit it.
 void Scene::buildBvh4() {
     // PT_BVH4_OPEN=0: open the first inner slot instead of the largest (build experiments)
     const char* eo = std::getenv("PT_BVH4_OPEN");
@@ -316,6 +317,9 @@ void Scene::buildBvh4() {
     for (size_t m = 0; m < meshes.size(); m++) {
         const int root = mesh_bvh_root[m];
         if (root < 0) continue;
+        // a mesh without triangles gets no 4-wide node either: root -1, which the traces skip at
+        // select (PT_EMPTY_SKIP) and bvh4_traverse returns from at once
+        if (meshes[m].triangle_indices.end_index <= meshes[m].triangle_indices.start_index) continue;
         const size_t n0 = bvh4_nodes.size();
         bool fits = true;
         // the mesh's first leaf record: its leaf entries are stored relative to it

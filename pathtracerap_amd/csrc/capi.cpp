@@ -216,7 +216,7 @@ pt_renderer* pt_renderer_create(const pt_render_config* c) {
         set_err("bad accel");
         return nullptr;
     }
-    if (c->block != 64 && c->block != 128 && c->block != 256) { set_err("block must be 64, 128 or 256"); return nullptr; }
+    // block: 64, 128 or 256; any other value falls back to 256 (Renderer::allocateOnGPU, kp.chunk)
     try {
         pt_renderer* r = new pt_renderer();
         r->r = new pt::Renderer(to_cfg(c));

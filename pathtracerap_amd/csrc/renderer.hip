@@ -2959,7 +2959,8 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     if (cfg.accel != ACCEL_GRID && scene.bvh_nodes.empty()) { last_error = "scene built without BVH"; return -1; }
     if (cfg.accel != ACCEL_GRID)     // every BLAS path walks the 4-wide BLAS: there is no binary fallback
         for (const ModelRec& m : scene.model_recs)
-            if (m.bvh_root >= 0 && (m.bvh4_root < 0 || scene.bvh4_nodes.empty())) {
+            if (m.bvh_root >= 0 && m.tri_end > m.tri_start &&      // an empty mesh has root -1 and is skipped at select
+                (m.bvh4_root < 0 || scene.bvh4_nodes.empty())) {
                 last_error = "a mesh has no 4-wide BLAS (a leaf of more than 31 triangles, 2^26 leaf records or more "
                              "in one mesh, or 2^27 4-wide nodes in the scene: beyond the traversal stacks' "
                              "encodings); use accel grid";
