@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 8
+#define PT_ABI_VERSION 9
 
 /* Primitive.h:70-79 Material::MaterialType */
 enum {
@@ -166,6 +166,25 @@ int pt_renderer_intersect_rays(pt_renderer *r, int n, const float *orig, const f
  * full certificates accepted-but-wrong (no counterpart in the reference: it
  * checks the exactness of Renderer.cpp:238-360's replacement). */
 int pt_renderer_certify_check(pt_renderer *r, int n, const float *orig, const float *dir, int *out4);
+/* Test hook (PT_ACCEL_BVH / PT_ACCEL_GRID_FAST with the split trace): runs a caller's ray
+ * batch through the persistent trace kernels as bounce 1 of an iteration runs them.  The
+ * n rays are written as bounce 0's survivors into pipeline 0's ray pool: block b (of `chunk`
+ * = config.block positions) holds block_counts[b] rays, ray k at the k-th occupied position
+ * in block order; block_counts = NULL: full blocks, then the remainder.  Then the real
+ * k_scan, the ray sort (when on) and the trace launches allocate_on_gpu picked (tails and
+ * k_trace_deferred included) run on the renderer's stream, and ray k's hit record is read
+ * back as the shading pass reads it: world distance (FLT_MAX: miss), world normal, model
+ * (-1: miss) and the scene triangle index.  Refused (negative return, message) before any
+ * launch: not allocated, another accel, PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0, n outside
+ * [0, width*height] (less the dropped tail with tail_drop), a count outside [0, chunk],
+ * counts that do not sum to n, n_blocks > ceil(width*height / chunk).  The image, the
+ * primary-hit cache and pt_renderer_segments / _segments_per_bounce are unchanged (but the
+ * deferred-ray slot and the fault counter, which count this trace too); fails like
+ * pt_renderer_synchronize when a trace gave up.  Zero-length and non-finite directions
+ * are outside the hook's contract, as they are outside the renderer's (ABI 9). */
+int pt_renderer_trace_rays(pt_renderer *r, int n, const float *orig, const float *dir,
+                           const int *block_counts, int n_blocks,
+                           float *dist, float *normal, int *model, int *tri);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

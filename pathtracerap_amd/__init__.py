@@ -108,6 +108,8 @@ EXPORTS = [
     ("pt_renderer_primary_hits", ctypes.c_int, [ctypes.c_void_p, _P_F, _P_F, _P_I]),
     ("pt_renderer_intersect_rays", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, _P_F, _P_I]),
     ("pt_renderer_certify_check", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_I]),
+    ("pt_renderer_trace_rays", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_I, ctypes.c_int,
+                                              _P_F, _P_F, _P_I, _P_I]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -416,6 +418,22 @@ class Renderer:
         out = np.zeros((len(o), 4), np.int32)
         _err(lib().pt_renderer_certify_check(self._h, len(o), _fp(o), _fp(dd), _ip(out)), "certify_check")
         return out
+
+    def trace_rays(self, orig, dirs, block_counts=None):
+        """Test hook (accel bvh / grid_fast): the rays through the persistent trace
+        kernels as bounce 1 of an iteration runs them (k_scan, ray sort, main and tail
+        launches, k_trace_deferred) -> (dist, normal, model, tri) per ray.
+        ``block_counts``: the survivor layout, rays per source block of ``cfg.block``
+        pool positions (None: dense)."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        dd = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = len(o)
+        t = np.zeros(n, np.float32); nn = np.zeros((n, 3), np.float32)
+        m = np.zeros(n, np.int32); tri = np.zeros(n, np.int32)
+        bc = None if block_counts is None else np.ascontiguousarray(block_counts, np.int32).reshape(-1)
+        _err(lib().pt_renderer_trace_rays(self._h, n, _fp(o), _fp(dd), None if bc is None else _ip(bc),
+                                          0 if bc is None else len(bc), _fp(t), _fp(nn), _ip(m), _ip(tri)), "trace_rays")
+        return t, nn, m, tri
 
     def free(self) -> None:
         if self._h:

@@ -310,6 +310,12 @@ int pt_renderer_certify_check(pt_renderer* r, int n, const float* o, const float
     if (n < 0 || (n > 0 && (!o || !d || !out4))) return set_err("bad arguments");
     R_CALL(r->r->certifyCheck(n, o, d, out4));
 }
+int pt_renderer_trace_rays(pt_renderer* r, int n, const float* o, const float* d, const int* block_counts, int n_blocks,
+                           float* t, float* nn, int* m, int* tri) {
+    if (n > 0 && (!o || !d || !t || !nn || !m || !tri)) return set_err("bad arguments");
+    if (block_counts && n_blocks < 0) return set_err("bad arguments");
+    R_CALL(r->r->traceRays(n, o, d, block_counts, n_blocks, t, nn, m, tri));
+}
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;

@@ -147,6 +147,11 @@ public:
     int intersectRays(int n, const float* orig, const float* dir, float* dist, float* normal, int* model);
     // test hook (grid_fast): walk certificates vs the exact walk on the same hit sets; 4 ints per ray
     int certifyCheck(int n, const float* orig, const float* dir, int* out4);
+    // test hook (split bvh / grid_fast): the caller's rays as bounce 0's survivors in pipeline 0's
+    // pool (block_counts: survivors per source block, null = dense), then bounce 1's k_scan / sort /
+    // persistent-trace launches over them; per ray the hit record the shading pass would read
+    int traceRays(int n, const float* orig, const float* dir, const int* block_counts, int n_blocks,
+                  float* dist, float* normal, int* model, int* tri);
 
     RenderConfig cfg;
     std::string last_error;
@@ -154,6 +159,7 @@ public:
 private:
     int launchPrimary();
     void launchTrace(const KParams& k, hipStream_t st, int b);
+    int enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace);
     void launchBounce(const KParams& k, hipStream_t st, bool first, dim3 grid, int iter, int b, int accel);
     int allocPipe(KParams& k, size_t cap, hipStream_t st);
     int fail(hipError_t e, const char* what);

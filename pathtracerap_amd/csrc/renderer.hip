@@ -2866,6 +2866,18 @@ __global__ __launch_bounds__(kSortWG) void k_sort_scatter(KParams p, int bounce)
         }
 }
 
+// Test hook (trace_rays): the hit records a persistent trace left for dense slots
+// 0..n-1, read as the shading pass reads them (get_hit), plus the triangle index.
+__global__ __launch_bounds__(kBlock) void k_gather_hits(KParams p, int n, float* dist, float* nrm, int* model, int* tri) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const Hit h = get_hit(p, j);
+    dist[j] = h.dist;
+    nrm[3 * j] = h.n.x; nrm[3 * j + 1] = h.n.y; nrm[3 * j + 2] = h.n.z;
+    model[j] = h.model;
+    tri[j] = __float_as_int(p.hit4[j].y);
+}
+
 __global__ void k_selftest_math(int n, const float* x, const float* y, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3325,6 +3337,30 @@ void Renderer::launchBounce(const KParams& k, hipStream_t st, bool first, dim3 g
     }
 }
 
+// Bounce b's ray sort (when the pipeline sorts) and persistent trace launches, as
+// every iteration enqueues them (and the trace_rays test hook).  pall / ptrace: an
+// event pair around the sort kernels / around the trace launches only.
+int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (k.order) {
+        if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
+        const dim3 sg((unsigned)((k.nblocks * (size_t)k.chunk + kSortWG * kSortPer - 1) / (kSortWG * kSortPer)));
+        hipLaunchKernelGGL(k_sort_hist, sg, dim3(kSortWG), 0, st, k, b);
+        hipLaunchKernelGGL(k_sort_prefix, dim3(1), dim3(kSortWG), 0, st, k);
+        hipLaunchKernelGGL(k_sort_scatter, sg, dim3(kSortWG), 0, st, k, b);
+        if (pall) { hipEventRecord(e1, st); sort_events.push_back({e0, e1}); e0 = e1 = nullptr; }
+    }
+    // the trace pair brackets the trace launches only (not the sort kernels)
+    if (ptrace) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
+    launchTrace(k, st, b);
+    PT_HIP(hipGetLastError());
+    if (ptrace) {
+        hipEventRecord(e1, st);
+        trace_events.push_back({e0, e1});
+    }
+    return 0;
+}
+
 // One iteration's bounce loop on pipeline q (stream st): sort / trace / shade /
 // scan per bounce.  iter = -1: k_bounce reads the id from k.iter_dev (capture).
 int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes) {
@@ -3336,23 +3372,7 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes) {
     for (int b = 0; b < passes; b++) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (b > 0 && split_trace) {
-            if (k.order) {
-                if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-                const dim3 sg((unsigned)((k.nblocks * (size_t)k.chunk + kSortWG * kSortPer - 1) / (kSortWG * kSortPer)));
-                hipLaunchKernelGGL(k_sort_hist, sg, dim3(kSortWG), 0, st, k, b);
-                hipLaunchKernelGGL(k_sort_prefix, dim3(1), dim3(kSortWG), 0, st, k);
-                hipLaunchKernelGGL(k_sort_scatter, sg, dim3(kSortWG), 0, st, k, b);
-                if (pall) { hipEventRecord(e1, st); sort_events.push_back({e0, e1}); e0 = e1 = nullptr; }
-            }
-            // the trace pair brackets the trace launches only (not the sort kernels)
-            if (ptrace) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-            launchTrace(k, st, b);
-            PT_HIP(hipGetLastError());
-            if (ptrace) {
-                hipEventRecord(e1, st);
-                trace_events.push_back({e0, e1});
-                e0 = e1 = nullptr;
-            }
+            if (enqueueSortTrace(k, st, b, pall, ptrace) != 0) return -1;
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             launchBounce(k, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
@@ -3660,6 +3680,100 @@ int Renderer::certifyCheck(int n, const float* orig, const float* dir, int* out4
     PT_HIP(hipStreamSynchronize(stream));
     hipFree(d_o); hipFree(d_d); hipFree(d_out);
     return 0;
+}
+
+// Test hook: the caller's rays become bounce 0's survivors in pipeline 0's pool
+// (block b's block_counts[b] rays at [b * chunk, b * chunk + cnt_b) of pool buffer 0,
+// ray k at the k-th occupied position), the real k_scan turns the counts into n_live[1] /
+// blk_off / dst_start, and bounce 1's sort and persistent-trace launches run over them as
+// in an iteration.  Returns each dense slot's hit record; slot k holds ray k (k_scan's
+// offsets keep the block-major order).  The renderer is left as after a finished bounce:
+// the per-bounce counters reset, segments[] restored but for the deferred-ray and fault slots.
+int Renderer::traceRays(int n, const float* orig, const float* dir, const int* block_counts, int n_blocks,
+                        float* dist, float* normal, int* model, int* tri) {
+    if (!allocated) { last_error = "trace_rays: not allocated"; return -1; }
+    if (cfg.accel != ACCEL_BVH && cfg.accel != ACCEL_GRID_FAST) {
+        last_error = "trace_rays needs accel bvh or grid_fast (the persistent traces)";
+        return -1;
+    }
+    if (!split_trace) { last_error = "trace_rays needs the split trace (PT_GF_SPLIT / PT_TRACE_SPLIT not 0)"; return -1; }
+    const KParams& k = pk[0];
+    const int CH = k.chunk;
+    const int nb_all = (k.npix + CH - 1) / CH;          // the blocks k_scan(bounce 0) reads
+    if (n < 0 || n > k.npix) { last_error = "trace_rays: n must be in [0, width * height]"; return -1; }
+    std::vector<int> cnt((size_t)k.nblocks + 1, 0);
+    if (block_counts) {
+        if (n_blocks < 0 || n_blocks > nb_all) { last_error = "trace_rays: more blocks than the frame has"; return -1; }
+        long long sum = 0;
+        for (int b = 0; b < n_blocks; b++) {
+            if (block_counts[b] < 0 || block_counts[b] > CH) {
+                last_error = "trace_rays: block_counts[" + std::to_string(b) + "] outside [0, chunk]";
+                return -1;
+            }
+            cnt[b] = block_counts[b];
+            sum += block_counts[b];
+        }
+        if (sum != n) { last_error = "trace_rays: block_counts do not sum to n"; return -1; }
+    } else {
+        for (int b = 0, left = n; left > 0; b++, left -= CH) cnt[b] = std::min(left, CH);
+    }
+    // the pool positions no ray occupies hold a harmless finite ray: a trace that read one
+    // would report its hit for the wrong slot, not run on whatever an earlier render left
+    const size_t cap = (size_t)k.nblocks * CH;
+    std::vector<float4> ro(cap, make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, -1)));
+    std::vector<float4> rd(cap, make_float4(0.0f, 0.0f, 1.0f, __builtin_bit_cast(float, 0)));
+    for (int b = 0, q = 0; b < k.nblocks; b++)
+        for (int r = 0; r < cnt[b]; r++, q++) {
+            const size_t i = (size_t)b * CH + r;
+            ro[i] = make_float4(orig[3 * q], orig[3 * q + 1], orig[3 * q + 2], __builtin_bit_cast(float, q));
+            rd[i] = make_float4(dir[3 * q], dir[3 * q + 1], dir[3 * q + 2], __builtin_bit_cast(float, 1));
+        }
+    // everything enqueued earlier has finished (renderLoop joined the pipelines into `stream`)
+    PT_HIP(hipStreamSynchronize(stream));
+    constexpr int kSeg = kDiagCounters + kMaxBounceCounters;
+    unsigned long long seg0[kSeg], seg1[kSeg];
+    PT_HIP(hipMemcpyAsync(seg0, k.segments, sizeof seg0, hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipMemcpyAsync(k.ray[0][0], ro.data(), cap * sizeof(float4), hipMemcpyHostToDevice, stream));
+    PT_HIP(hipMemcpyAsync(k.ray[0][1], rd.data(), cap * sizeof(float4), hipMemcpyHostToDevice, stream));
+    PT_HIP(hipMemcpyAsync(k.blk_cnt, cnt.data(), (size_t)k.nblocks * sizeof(int), hipMemcpyHostToDevice, stream));
+    PT_HIP(hipStreamSynchronize(stream));               // the host vectors are pageable
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanWG), 0, stream, k, 0);
+    PT_HIP(hipGetLastError());
+    if (enqueueSortTrace(k, stream, 1, false, false) != 0) return -1;
+    float* d_out = nullptr;                              // dist n, normal 3n, model n, tri n
+    if (n > 0) {
+        PT_HIP(hipMalloc(&d_out, (size_t)n * 24));
+        float* d_t = d_out;
+        float* d_n = d_out + n;
+        int* d_m = reinterpret_cast<int*>(d_out + 4 * (size_t)n);
+        int* d_tri = d_m + n;
+        hipLaunchKernelGGL(k_gather_hits, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, k, n,
+                           d_t, d_n, d_m, d_tri);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(dist, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(model, d_m, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        hipFree(d_out);
+        if (e != hipSuccess) return fail(e, "trace_rays: gather");
+    }
+    // what k_scan resets at the end of a bounce (no shading pass and no scan follow this trace)
+    PT_HIP(hipMemsetAsync(k.trace_next, 0, sizeof(int), stream));
+    PT_HIP(hipMemsetAsync(k.hs_pool_next, 0, sizeof(int), stream));
+    PT_HIP(hipMemsetAsync(k.defer_count, 0, sizeof(int), stream));
+    PT_HIP(hipMemsetAsync(k.cont_count, 0, 2 * kDrainLevels * sizeof(int), stream));
+    PT_HIP(hipMemsetAsync(k.cont_next, 0, kDrainLevels * sizeof(int), stream));
+    if (k.order) PT_HIP(hipMemsetAsync(k.sort_bins, 0, 2 * kSortBins * sizeof(int), stream));
+    // segments[]: k_scan counted the frame's pixels as bounce 0's rays; put the counters back,
+    // keeping what this trace added to the deferred-ray and fault slots
+    PT_HIP(hipMemcpyAsync(seg1, k.segments, sizeof seg1, hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    seg0[kDeferredRayCounter] = seg1[kDeferredRayCounter];
+    seg0[kTraceFaultCounter] = seg1[kTraceFaultCounter];
+    PT_HIP(hipMemcpyAsync(k.segments, seg0, sizeof seg0, hipMemcpyHostToDevice, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    return checkFaults();
 }
 
 int selftest_math(int n, const float* x, const float* y, float* out, std::string* err) {

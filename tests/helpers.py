@@ -38,3 +38,18 @@ def assert_bitexact(got, want, what):
         i = bad[0]
         raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at flat {i}: "
                              f"got {got.reshape(-1)[i]!r} want {want.reshape(-1)[i]!r}")
+
+
+def room_rays(n, seed, center=(0.0, 100.0, 0.0), spread=600.0):
+    """Seeded rays with origins in a cube about `center` (at the reference room's
+    size: on, near and outside its walls) and normal directions, a quarter of
+    them with zero components or axis-aligned."""
+    rs = np.random.RandomState(seed)
+    o = (rs.uniform(-1, 1, (n, 3)) * spread + np.array(center)).astype(np.float32)
+    d = rs.normal(size=(n, 3)).astype(np.float32)
+    # axis-aligned and zero-component directions (the reference's == 0 branches)
+    d[: n // 8, 0] = 0.0
+    d[n // 8: n // 4, 1] = 0.0
+    d[n // 4: n // 4 + n // 16, :2] = 0.0
+    d[n // 4 + n // 16: n // 4 + n // 8] = np.float32([0, -1, 0])
+    return o, d

@@ -1,8 +1,10 @@
 """Scene builders, ray generators and a host-side traversal emulator for the
 trace and compaction paths that the scheduling tests never reach (deep
 traversal stacks, hit sets beyond LDS, grids other than 25^3, the model-count
-variants, empty meshes).  Test infrastructure: used by test_path_scenes.py
-(CPU preconditions) and test_gpu_paths.py (GPU == oracle, bit for bit)."""
+variants, empty meshes), and the named ray sets, direction scalings and
+survivor layouts that go through Renderer.trace_rays.  Test infrastructure:
+used by test_path_scenes.py (CPU preconditions), test_gpu_paths.py and
+test_gpu_trace_rays.py (GPU == oracle, bit for bit)."""
 import numpy as np
 
 from helpers import assert_bitexact, flat_from_export, oracle_cfg
@@ -362,6 +364,228 @@ def empty_mesh_spec(where="first", vertices=True, minimal=True):
     at = {"first": 0, "middle": len(models) // 2, "last": len(models)}[where]
     models.insert(at, empty)
     return meshes, models, at
+
+
+# ---------------------------------------------------------------------------
+# H. ray batches for Renderer.trace_rays (the persistent traces on caller rays)
+# ---------------------------------------------------------------------------
+
+def _stack_rays_mesh(n, seed, half=20000.0, planes=8):
+    """Mesh-space (x1000 units) rays of stack_rays: origins on planes 0..planes-1
+    of the geometric stack (z = r^k; every other one between two planes, where the
+    equal quads do not answer at distance 0), x and y in the inner quarter of the full quads'
+    footprint (outside the tapered stack's near quads, of a tenth, for 7 in 8),
+    cosine-weighted directions about +z, along which the planes follow."""
+    rs = np.random.RandomState(seed)
+    k = rs.randint(0, planes, n) + 0.5 * (np.arange(n) % 2)     # every other origin half way to the next plane
+    o = np.c_[rs.uniform(-0.25, 0.25, (n, 2)) * half, np.power(STACK_R, k)]
+    return o, cosine_directions(n, seed + 1)
+
+
+def stack_rays(a, n, seed):
+    """World-space rays for the stack scenes (model 0 is the DIFFUSE stack)."""
+    o, d = _stack_rays_mesh(n, seed)
+    return to_world(a, 0, o).astype(np.float32), to_world(a, 0, d, 0.0).astype(np.float32)
+
+
+def empty_model_rays(n=20000):
+    """The rays of test_intersect_rays_never_reports_the_empty_model."""
+    o, d = random_rays(n, 8, center=(0.0, 200.0, 0.0), spread=450.0)
+    o[:2000] = np.float32([50, 100, 600])
+    d[:2000] = np.float32([50, 100, 100]) - o[:2000] + np.random.RandomState(2).normal(size=(2000, 3)).astype(np.float32) * 40
+    return o, d
+
+
+def room_interior_rays(a, n, seed):
+    """interior_rays inside the model with the largest mesh box times scale (the
+    reference scene's enclosing room)."""
+    ext = []
+    for i in range(len(a["model_ints"])):
+        bb = a["mesh_bbox"].reshape(-1, 6).astype(np.float64)[a["model_ints"][i, 0]]
+        ext.append(np.abs(to_world(a, i, (bb[3:] - bb[:3])[None], 0.0)).sum())
+    return interior_rays(a, n, seed, model=int(np.argmax(ext)))
+
+
+SCALINGS = ["pow2", "reflect", "tiny", "wide"]
+
+
+def scaled(d, kind, seed):
+    """Directions times a per-ray positive factor: bounce directions are not unit
+    vectors (reflect_ref gives n (1 - 2 d.n) terms of any length in [0, 3])."""
+    rs = np.random.RandomState(seed)
+    n = len(d)
+    if kind == "pow2":
+        f = np.ldexp(1.0, rs.randint(-20, 21, n))
+    elif kind == "reflect":
+        c = rs.uniform(-1, 1, n)
+        c[c == 0.0] = 0.5
+        f = np.abs(1.0 - 2.0 * c)
+        f[f == 0.0] = 1.0
+    elif kind == "tiny":
+        f = 10.0 ** rs.uniform(-6, -3, n)
+    elif kind == "wide":
+        f = 10.0 ** rs.uniform(-6, 6, n)
+    else:
+        raise ValueError(kind)
+    out = (np.asarray(d, np.float32) * f.astype(np.float32)[:, None]).astype(np.float32)
+    assert np.isfinite(out).all() and (np.abs(out).max(1) > 0).all()
+    return out
+
+
+SCAN_TILE = 4096            # k_scan: kScanWG x kScanPer block counts per tile
+
+
+def layouts(n_slots, chunk, n, seed):
+    """Named survivor layouts for trace_rays: block_counts over the ceil(n_slots /
+    chunk) source blocks of a frame of n_slots pixels.  Every layout carries n
+    rays but `islands`, which holds one ray per island (use the first
+    counts.sum() rays); `tile_gap` is there only when the frame has the blocks."""
+    nb = (n_slots + chunk - 1) // chunk
+    assert 0 < n <= n_slots
+    rs = np.random.RandomState(seed)
+    out = {}
+    full, rem = divmod(n, chunk)
+    c = np.zeros(nb, np.int32)
+    c[:full] = chunk
+    if rem:
+        c[full] = rem
+    out["dense"] = c
+    # random: blocks in random order take a count uniform in 0..chunk until n is placed
+    c = np.zeros(nb, np.int32)
+    left = n
+    for b in rs.permutation(nb):
+        c[b] = min(left, rs.randint(0, chunk + 1))
+        left -= c[b]
+        if left == 0:
+            break
+    for b in range(nb):                     # n beyond what the draws placed: top up in block order
+        add = min(left, chunk - c[b])
+        c[b] += add
+        left -= add
+    out["random"] = c
+    # islands: one ray in every 97th block, the first and the last block empty
+    c = np.zeros(nb, np.int32)
+    first = max(1, min(48, (nb - 1) // 2))
+    c[np.arange(first, nb - 1, 97)[:n]] = 1
+    if c.sum():
+        out["islands"] = c
+    # tile_gap: block 0 full, a whole scan tile's worth of empty blocks, then full blocks
+    need = 1 + SCAN_TILE + (max(n - chunk, 0) + chunk - 1) // chunk
+    if n > chunk and need <= nb:
+        c = np.zeros(nb, np.int32)
+        c[0] = chunk
+        f2, r2 = divmod(n - chunk, chunk)
+        c[1 + SCAN_TILE: 1 + SCAN_TILE + f2] = chunk
+        if r2:
+            c[1 + SCAN_TILE + f2] = r2
+        out["tile_gap"] = c
+    # last: every ray in the final blocks (the partial block first, the last block full)
+    c = np.zeros(nb, np.int32)
+    if full:
+        c[nb - full:] = chunk
+    if rem:
+        c[nb - full - 1] = rem
+    out["last"] = c
+    # ragged: 1, chunk - 1, 1, chunk - 1, ...
+    c = np.zeros(nb, np.int32)
+    left = n
+    for b in range(nb):
+        c[b] = min(left, 1 if b % 2 == 0 else chunk - 1)
+        left -= c[b]
+    if left == 0:
+        out["ragged"] = c
+    return out
+
+
+_SCENES = {}
+
+
+def scene_once(key, make):
+    """One build per scene key and process."""
+    if key not in _SCENES:
+        _SCENES[key] = make()
+    return _SCENES[key]
+
+
+def _ref_scene(P):
+    from conftest import REF_SCENE
+
+    def make():
+        s = P.Scene(REF_SCENE)
+        s.build(bvh=True)
+        return s
+    return scene_once("ref", make)
+
+
+def _grid_id(grid):
+    return "x".join(str(g) for g in grid)
+
+
+def _ray_set_table():
+    """name -> (scene(P), grid, rays(export), hit-share floor of the one-lane tests)."""
+    from helpers import room_rays
+    g25 = (25, 25, 25)
+    t = {"ref": (_ref_scene, g25, lambda a: room_rays(40000, 11, center=(25.0, 380.0, 0.0), spread=480.0), 0.3)}
+    for grid in GRIDS:
+        for xf in (False, True):
+            t[f"boundary-{_grid_id(grid)}-{'xf' if xf else 'id'}"] = (
+                lambda P, grid=grid, xf=xf: scene_once(("boundary", grid, xf), lambda: boundary_scene(P, grid, xf)), grid,
+                lambda a, grid=grid: tuple(np.concatenate(p) for p in zip(boundary_rays(a, 20000, 5, grid),
+                                                                          interior_rays(a, 20000, 6))), 0.3)
+    t["comb"] = (lambda P: scene_once("comb_pair", lambda: comb_pair_scene(P)), g25,
+                 lambda a: tuple(np.concatenate(p) for p in zip(comb_axis_rays(a, 20000, 9), random_rays(20000, 4))), 0.2)
+    for k in MODEL_COUNTS:
+        t[f"models-{k}"] = (lambda P, k=k: scene_once(("models", k), lambda: scene_from_spec(P, *model_count_spec(k))), g25,
+                            lambda a: random_rays(20000, 8, center=(0.0, 200.0, 0.0), spread=450.0), 0.2)
+    for where in ("first", "middle", "last"):
+        t[f"empty-{where}"] = (
+            lambda P, where=where: scene_once(("empty", where, True),
+                                              lambda: scene_from_spec(P, *empty_mesh_spec(where)[:2])), g25,
+            lambda a: empty_model_rays(), 0.2)
+    t["stack-tapered"] = (lambda P: scene_once(("stack", STACK_TAPER), lambda: stack_scene(P, STACK_TAPER)), g25,
+                          lambda a: stack_rays(a, 20000, 21), 0.2)
+    t["stack-dense"] = (lambda P: scene_once(("stack", "dense"), lambda: dense_stack_scene(P)), g25,
+                        lambda a: stack_rays(a, 20000, 21), 0.2)
+    return t
+
+
+RAY_SET_NAMES = (["ref"] + [f"boundary-{_grid_id(g)}-{x}" for g in GRIDS for x in ("id", "xf")] + ["comb"] +
+                 [f"models-{k}" for k in MODEL_COUNTS] + [f"empty-{w}" for w in ("first", "middle", "last")] +
+                 ["stack-tapered", "stack-dense"])
+_RAY_SETS = {}
+_RAY_ORACLE = {}
+
+
+def ray_set(P, name):
+    """(scene, grid, origins, directions, hit-share floor) of a named ray set, built once."""
+    if name not in _RAY_SETS:
+        make, grid, rays, floor = _ray_set_table()[name]
+        s = make(P)
+        o, d = rays(s.export())
+        o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
+        assert np.isfinite(o).all() and np.isfinite(d).all() and (np.abs(d).max(1) > 0).all()
+        o.setflags(write=False); d.setflags(write=False)
+        _RAY_SETS[name] = (s, grid, o, d, floor)
+    return _RAY_SETS[name]
+
+
+def oracle_hits(O, key, scene, o, d, accel, grid=(25, 25, 25)):
+    """The oracle's (dist, normal, model) for a ray batch, computed once per (key,
+    oracle accel) and shared, unchanged, among the tests.  `accel` is the GPU's:
+    the reference grid for 0 and 2, the exhaustive closest hit for 1."""
+    from helpers import oracle_accel
+    oa = oracle_accel(accel)
+    if (key, oa) not in _RAY_ORACLE:
+        r = O.intersect_rays(flat_from_export(scene.export(), grid), o, d, accel=oa, threads=16)
+        for v in r:
+            v.setflags(write=False)
+        _RAY_ORACLE[(key, oa)] = r
+    return _RAY_ORACLE[(key, oa)]
+
+
+def ray_set_oracle(P, O, name, accel):
+    s, grid, o, d, _ = ray_set(P, name)
+    return oracle_hits(O, name, s, o, d, accel, grid)
 
 
 # ---------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import REF_SCENE
 from helpers import assert_bitexact, flat_from_export, oracle_accel, oracle_cfg
+from helpers import room_rays as _random_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -121,18 +122,6 @@ def test_repeatable(gpu, pt_mod):
         imgs.append(r.image())
         r.free()
     assert_bitexact(imgs[0], imgs[1], "rerun")
-
-
-def _random_rays(n, seed, center=(0.0, 100.0, 0.0), spread=600.0):
-    rs = np.random.RandomState(seed)
-    o = (rs.uniform(-1, 1, (n, 3)) * spread + np.array(center)).astype(np.float32)
-    d = rs.normal(size=(n, 3)).astype(np.float32)
-    # axis-aligned and zero-component directions (the reference's == 0 branches)
-    d[: n // 8, 0] = 0.0
-    d[n // 8: n // 4, 1] = 0.0
-    d[n // 4: n // 4 + n // 16, :2] = 0.0
-    d[n // 4 + n // 16: n // 4 + n // 8] = np.float32([0, -1, 0])
-    return o, d
 
 
 @pytest.mark.parametrize("accel", [0, 1, 2])

@@ -1,6 +1,8 @@
-"""CPU preconditions of test_gpu_paths.py: the scenes of path_scenes.py reach
-the paths they are built for (emulated traversal depths, the oracle's segment
-floor), and scenes with empty meshes build exactly as the oracle builds them."""
+"""CPU preconditions of test_gpu_paths.py and test_gpu_trace_rays.py: the scenes
+of path_scenes.py reach the paths they are built for (emulated traversal
+depths, the oracle's segment floor), scenes with empty meshes build exactly as
+the oracle builds them, and the ray sets, scaled directions and survivor
+layouts of the trace_rays tests are what those tests take them for."""
 import numpy as np
 import pytest
 
@@ -108,6 +110,101 @@ def test_model_count_scene_builds_as_the_oracle(pt_mod, oracle_mod, k):
     assert s.counts()["nmodel"] == k
     assert {m["material"] for m in models} >= {"DIFFUSE", "EMISSIVE"}
     _compare(s.export(), S.oracle_scene_from_spec(oracle_mod, meshes, models))
+
+
+# --- ray batches and survivor layouts of test_gpu_trace_rays.py -------------------
+
+@pytest.mark.parametrize("accel", [0, 1], ids=["grid", "bvh"])
+@pytest.mark.parametrize("name", S.RAY_SET_NAMES)
+def test_ray_sets_hit_share(pt_mod, oracle_mod, name, accel):
+    """Each ray set of the trace_rays tests hits on more than the share the
+    one-lane tests ask of the same generators (0.3 reference and boundary scenes,
+    0.2 elsewhere), on the reference grid and on the exact closest hit; the
+    oracle's result is the one the GPU tests compare with."""
+    _, _, o, d, floor = S.ray_set(pt_mod, name)
+    assert 20000 <= len(o) <= 40000
+    t, n, m = S.ray_set_oracle(pt_mod, oracle_mod, name, accel)
+    share = (m >= 0).mean()
+    print(f"ray set {name} oracle accel={accel}: {len(o)} rays, hit share {share:.4f}")
+    assert share > floor, share
+
+
+@pytest.mark.parametrize("variant", ["tapered", "dense"])
+def test_stack_rays_spill(pt_mod, variant):
+    """stack_rays: origins on the first planes inside the quads' footprint; of
+    the first 256, at least half emulate to kStack + 4 = 28 entries
+    (k_trace_bvh spills; k_trace_gf's 12 overflow before that), none beyond the
+    spill area, and most origins lie outside the tapered stack's near quads."""
+    P = pt_mod
+    s, _, o, d, _ = S.ray_set(P, f"stack-{variant}")
+    om, dm = S._stack_rays_mesh(len(o), 21)
+    assert_bitexact(S.to_world(s.export(), 0, om).astype(np.float32), o, "origins")
+    assert (np.abs(om[:, :2]) <= 20000.0).all() and (np.abs(om[:, :2]).max(1) > 2000.0).mean() > 0.5
+    assert (om[:, 2] >= 1.0).all() and (om[:, 2] <= S.STACK_R ** 8).all()
+    b4 = s.export_bvh4()
+    depth = np.array([S.emulate_stack_depth(b4, 0, om[i], dm[i]) for i in range(256)])
+    print(f"stack_rays {variant}: depth median {np.median(depth)}, min {depth.min()}, max {depth.max()}")
+    assert (depth >= 28).mean() >= 0.5, (np.median(depth), (depth >= 28).mean())
+    assert depth.max() <= 12 + 64
+
+
+@pytest.mark.parametrize("accel", [0, 1], ids=["grid", "bvh"])
+def test_scaled_directions_keep_the_oracle_result(pt_mod, oracle_mod, accel):
+    """20 000 rays from inside the reference room with their directions scaled
+    (scaled(): powers of two, reflect_ref's |1 - 2c|, 1e-6..1e-3, 1e-6..1e6): more
+    than half hit at every scaling, and a power-of-two factor leaves the oracle's
+    distance bit-identical and the model identical for every ray (both normalise
+    the direction first; a power of two scales it exactly).  The other kinds
+    round differently: the share of rays whose model changes and the largest
+    relative distance change are printed, not asserted."""
+    P, O = pt_mod, oracle_mod
+    s = S._ref_scene(P)
+    o, d = S.room_interior_rays(s.export(), 20000, 31)
+    t0, _, m0 = S.oracle_hits(O, "scaled-none", s, o, d, accel)
+    assert (m0 >= 0).mean() > 0.5
+    for i, kind in enumerate(S.SCALINGS):
+        dk = S.scaled(d, kind, 40 + i)
+        assert not np.array_equal(dk, d)
+        t, _, m = S.oracle_hits(O, f"scaled-{kind}", s, o, dk, accel)
+        share = (m >= 0).mean()
+        both = (m >= 0) & (m0 >= 0)
+        rel = np.abs(t[both].astype(np.float64) - t0[both]) / t0[both]
+        print(f"scaled {kind} oracle accel={accel}: hit share {share:.4f}, model differs on {(m != m0).sum()} rays, "
+              f"max relative distance change {rel.max():.3g}")
+        assert share > 0.5, share
+        if kind == "pow2":
+            assert_bitexact(t, t0, "pow2 distance")
+            assert_bitexact(m, m0, "pow2 model")
+
+
+@pytest.mark.parametrize("n_slots,chunk,n", [(640 * 512, 64, 20000), (128 * 96, 128, 4000), (128 * 96, 256, 4000),
+                                             (64 * 48, 64, 3072), (130, 64, 1)])
+def test_layouts_are_valid_block_counts(n_slots, chunk, n):
+    """Every count in [0, chunk], the counts sum to the rays the layout carries
+    (n; islands: one per island), over exactly the frame's blocks; at 5120 blocks
+    tile_gap and islands reach past one k_scan tile of 4096 counts, tile_gap
+    with a run of at least 4096 empty blocks across the tile boundary."""
+    nb = (n_slots + chunk - 1) // chunk
+    L = S.layouts(n_slots, chunk, n, 3)
+    assert {"dense", "random", "last"} <= set(L)
+    for name, c in L.items():
+        assert c.dtype == np.int32 and len(c) == nb, name
+        assert c.min() >= 0 and c.max() <= chunk, name
+        assert c.sum() == (n if name != "islands" else min(n, (c > 0).sum())), (name, c.sum())
+    if 2 * chunk < n <= n_slots // 2:
+        assert len({c.tobytes() for c in L.values()}) == len(L)       # all different
+        assert "ragged" in L and set(L["ragged"][:4].tolist()) == {1, chunk - 1}
+        assert L["last"][-1] == chunk and L["last"][0] == 0 and L["dense"][0] == chunk and L["dense"][-1] == 0
+        r = L["random"]
+        assert len(np.unique(r[r > 0])) > min(chunk, (r > 0).sum()) // 4       # many different counts
+    if nb > S.SCAN_TILE + 400:
+        g = L["tile_gap"]
+        assert g[0] == chunk and not g[1:1 + S.SCAN_TILE].any() and g[1 + S.SCAN_TILE] == chunk
+        assert np.nonzero(g)[0].max() > S.SCAN_TILE               # full blocks in the second tile
+        i = np.nonzero(L["islands"])[0]
+        assert i[0] > 0 and i[-1] < nb - 1 and (np.diff(i) == 97).all() and i[-1] - i[0] > S.SCAN_TILE
+    else:
+        assert "tile_gap" not in L
 
 
 @pytest.mark.parametrize("transformed", [False, True])
