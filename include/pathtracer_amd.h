@@ -185,6 +185,55 @@ int pt_renderer_certify_check(pt_renderer *r, int n, const float *orig, const fl
 int pt_renderer_trace_rays(pt_renderer *r, int n, const float *orig, const float *dir,
                            const int *block_counts, int n_blocks,
                            float *dist, float *normal, int *model, int *tri);
+
+/* ---- Noise estimate and render-until-converged (no counterpart in the reference,
+ * which always renders ITER samples).  Off unless pt_renderer_enable_moments is
+ * called: a render then launches, allocates and computes exactly what it did. ---- */
+#define PT_NOISE_TILE 16
+/* Keep, beside the image, the per-pixel sum of squared contributions (W*H*3 floats):
+ * one fused pass per iteration adds a contribution c to the image and c*c to the
+ * moments, in iteration order, so both are bit-reproducible and the same for every
+ * pipeline count; the image is unchanged.  device_m2 = NULL: the renderer allocates
+ * the buffer; otherwise the caller owns it, as with pt_renderer_bind_image (16-byte
+ * aligned image and moment buffers take the wide-access kernel).  Costs 12 bytes per
+ * pixel, plus one contribution buffer of the same size when pipelines == 1.  Must be
+ * called before pt_renderer_allocate_on_gpu ("enable_moments must precede
+ * allocateOnGPU").  pt_renderer_clear_image zeroes the moments and the sample count
+ * (iterations enqueued since allocate_on_gpu or the last clear); pixels dropped by
+ * tail_drop keep moment 0.  No counterpart in the reference. */
+int pt_renderer_enable_moments(pt_renderer *r, float *device_m2);
+/* The moments, ordered and fault-checked like pt_renderer_read_image; fails with
+ * "moments not enabled" when they are off.  No counterpart in the reference. */
+int pt_renderer_read_moments(pt_renderer *r, float *host_m2);
+/* Relative noise of the accumulated image from S = image, Q = moments and
+ * nf = (float)samples (samples <= 0: the sample count; fewer than 2 is refused with
+ * "need at least 2 samples").  Per pixel, in float32 and in this order:
+ *   for k in r,g,b:  m_k = S_k / nf;  q = Q_k / nf;  v = q - m_k*m_k;  v = v > 0 ? v : 0;
+ *                    e_k = sqrtf(v / (nf - 1.0f));         (standard error of the mean)
+ *   err = ((e_r + e_g) + e_b) / (((m_r + m_g) + m_b) + 0.01f);
+ * Tiles are PT_NOISE_TILE x PT_NOISE_TILE pixels, ceil(W/16) x ceil(H/16), row-major,
+ * partial in the last tile column and row: tile sum = sum of (double)err over its pixels,
+ * tile_err = (float)(tile sum / pixels in the tile), *mean_err = (sum of tile sums) /
+ * (W*H) in double, *max_tile_err = the largest tile_err; tile_err_host (may be NULL)
+ * receives the tile map.  The reductions use no atomics: a run repeats bit for bit.
+ * Runs on the renderer's stream, synchronizes, and fails like pt_renderer_read_image
+ * after a trace fault.
+ * Limit: the raw-moment variance q - m*m cancels in float32, with a floor of about
+ * 1e-7 * m*m; this is an estimate to stop a render by, not a statistic.
+ * No counterpart in the reference. */
+int pt_renderer_noise(pt_renderer *r, int samples, double *mean_err, float *max_tile_err,
+                      float *tile_err_host);
+/* Renders iterations first_iter, first_iter + 1, ... in chunks of check_every (<= 0:
+ * 32; the last chunk is cut at max_iters); after each chunk that brings this call's
+ * count to max(min_iters, 2) or more it evaluates pt_renderer_noise over every sample
+ * in the accumulator and stops when mean_err <= target.  Returns 1 converged, 0
+ * max_iters reached, < 0 error; *iters_done = iterations this call rendered,
+ * *mean_err = the last estimate (-1: fewer than 2 samples).  Each check costs a
+ * synchronize and the start/end ramp of a render_loop call: check_every 32 keeps that
+ * to a few percent of the chunk.  Moments must be enabled.  No counterpart in the
+ * reference. */
+int pt_renderer_render_until(pt_renderer *r, int first_iter, int min_iters, int max_iters,
+                             int check_every, double target, int *iters_done, double *mean_err);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

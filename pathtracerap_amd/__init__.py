@@ -32,6 +32,7 @@ _LIB_PATH = os.environ.get("PT_LIB_PATH") or os.path.join(_HERE, "libpathtracer_
 ACCEL_GRID = 0
 ACCEL_BVH = 1
 ACCEL_GRID_FAST = 2
+NOISE_TILE = 16     # PT_NOISE_TILE: Renderer.noise()'s tile edge in pixels
 # renderer.h: segments[] slots after the per-bounce counters, as segments_per_bounce indices
 _MAX_BOUNCE_COUNTERS = 64
 _DEFERRED_SLOT = 50 + _MAX_BOUNCE_COUNTERS - 1     # kDeferredRayCounter
@@ -110,6 +111,11 @@ EXPORTS = [
     ("pt_renderer_certify_check", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_I]),
     ("pt_renderer_trace_rays", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_I, ctypes.c_int,
                                               _P_F, _P_F, _P_I, _P_I]),
+    ("pt_renderer_enable_moments", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    ("pt_renderer_read_moments", ctypes.c_int, [ctypes.c_void_p, _P_F]),
+    ("pt_renderer_noise", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _P_F, _P_F]),
+    ("pt_renderer_render_until", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_double, _P_I, ctypes.POINTER(ctypes.c_double)]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -324,6 +330,7 @@ class Renderer:
         if not self._h:
             _err(-1, "pt_renderer_create")
         self._image_ref = None
+        self._m2_ref = None
 
     def set_stream(self, hip_stream: int) -> None:
         _err(lib().pt_renderer_set_stream(self._h, ctypes.c_void_p(int(hip_stream))), "set_stream")
@@ -434,6 +441,39 @@ class Renderer:
         _err(lib().pt_renderer_trace_rays(self._h, n, _fp(o), _fp(dd), None if bc is None else _ip(bc),
                                           0 if bc is None else len(bc), _fp(t), _fp(nn), _ip(m), _ip(tri)), "trace_rays")
         return t, nn, m, tri
+
+    def enable_moments(self, device_ptr: int | None = None, keepalive=None) -> None:
+        """Keep the per-pixel sum of squared contributions beside the image (before
+        allocateOnGPU).  ``device_ptr``: a caller-owned W*H*3 float buffer (a torch
+        tensor, kept alive by ``keepalive``); None: the renderer allocates it."""
+        self._m2_ref = keepalive
+        _err(lib().pt_renderer_enable_moments(self._h, ctypes.c_void_p(int(device_ptr)) if device_ptr else None),
+             "enable_moments")
+
+    def moments(self) -> np.ndarray:
+        out = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
+        _err(lib().pt_renderer_read_moments(self._h, _fp(out)), "read_moments")
+        return out
+
+    def noise(self, samples: int | None = None) -> dict:
+        """Relative noise estimate of the accumulated image (include/pathtracer_amd.h,
+        pt_renderer_noise): ``mean`` over the frame, ``max_tile`` and the ``tiles``
+        map, (ceil(H/16), ceil(W/16)) float32.  ``samples``: None = the iterations
+        rendered since allocateOnGPU / clearImage."""
+        ty, tx = (self.cfg.height + NOISE_TILE - 1) // NOISE_TILE, (self.cfg.width + NOISE_TILE - 1) // NOISE_TILE
+        tiles = np.zeros((ty, tx), np.float32)
+        mean, mx = ctypes.c_double(), ctypes.c_float()
+        _err(lib().pt_renderer_noise(self._h, int(samples or 0), ctypes.byref(mean), ctypes.byref(mx), _fp(tiles)), "noise")
+        return dict(mean=mean.value, max_tile=np.float32(mx.value), tiles=tiles)
+
+    def render_until(self, target: float, max_iters: int, min_iters: int = 2, check_every: int = 32,
+                     first_iter: int = 0):
+        """Render in chunks of ``check_every`` iterations until the mean noise estimate
+        is at most ``target`` or ``max_iters`` are done -> (converged, iters, mean)."""
+        done, mean = ctypes.c_int(), ctypes.c_double()
+        rc = _err(lib().pt_renderer_render_until(self._h, int(first_iter), int(min_iters), int(max_iters), int(check_every),
+                                                 float(target), ctypes.byref(done), ctypes.byref(mean)), "render_until")
+        return bool(rc), done.value, mean.value
 
     def free(self) -> None:
         if self._h:

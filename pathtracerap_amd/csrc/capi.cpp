@@ -316,6 +316,18 @@ int pt_renderer_trace_rays(pt_renderer* r, int n, const float* o, const float* d
     if (block_counts && n_blocks < 0) return set_err("bad arguments");
     R_CALL(r->r->traceRays(n, o, d, block_counts, n_blocks, t, nn, m, tri));
 }
+int pt_renderer_enable_moments(pt_renderer* r, float* device_m2) { R_CALL(r->r->enableMoments(device_m2)); }
+int pt_renderer_read_moments(pt_renderer* r, float* h) {
+    if (!h) return set_err("null buffer");
+    R_CALL(r->r->readMoments(h));
+}
+int pt_renderer_noise(pt_renderer* r, int samples, double* mean_err, float* max_tile_err, float* tile_err_host) {
+    R_CALL(r->r->noise(samples, mean_err, max_tile_err, tile_err_host));
+}
+int pt_renderer_render_until(pt_renderer* r, int first_iter, int min_iters, int max_iters, int check_every,
+                             double target, int* iters_done, double* mean_err) {
+    R_CALL(r->r->renderUntil(first_iter, min_iters, max_iters, check_every, target, iters_done, mean_err));
+}
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;

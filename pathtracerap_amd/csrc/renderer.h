@@ -75,7 +75,8 @@ struct KParams {
     int trace_flags;                    // k_trace_bvh variant: 11 LDS model records, 10 global
     int* defer_slots;                   // k_trace_gf: slots whose hit set overflowed LDS (k_trace_deferred)
     int* defer_count;                   // reset by k_scan
-    float* contrib;                     // pipelines > 1: this pipeline's per-iteration contributions (k_merge)
+    float* contrib;                     // pipelines > 1 or moments on: this pipeline's per-iteration contributions
+                                        // (k_merge / k_merge_m2); null: k_bounce adds straight into the image
     int2* order;                        // ray sort: claim position -> (dense slot, source index); null: claim order
     int* sort_bins;                     // [kSortBins] rays per key, [kSortBins] scatter cursors; zeroed by k_scan
     unsigned short* sort_key;           // per source index of the previous bounce's pool
@@ -152,6 +153,15 @@ public:
     // persistent-trace launches over them; per ray the hit record the shading pass would read
     int traceRays(int n, const float* orig, const float* dir, const int* block_counts, int n_blocks,
                   float* dist, float* normal, int* model, int* tri);
+    // film.hip: per-pixel second moment of the contributions, the noise estimate read from it
+    // and render-until-converged (no counterpart in the reference)
+    int enableMoments(float* device_m2);             // before allocateOnGPU; null: own buffer
+    int readMoments(float* host_m2);
+    int noise(int samples, double* mean_err, float* max_tile_err, float* tile_err_host);
+    int renderUntil(int first_iter, int min_iters, int max_iters, int check_every, double target,
+                    int* iters_done, double* mean_err);
+    int noiseTilesX() const { return (cfg.width + 15) / 16; }      // PT_NOISE_TILE
+    int noiseTilesY() const { return (cfg.height + 15) / 16; }
 
     RenderConfig cfg;
     std::string last_error;
@@ -168,8 +178,10 @@ private:
     void dropGraphs();
     int joinPipes(int np);
     int checkFaults();
+    int allocMoments();
+    int launchMergeM2(const KParams& k, hipStream_t st);
 
-    KParams kp{};                    // pipeline 0 (and everything the pipelines share)
+    KParams kp{};                   // pipeline 0 (and everything the pipelines share)
     hipStream_t stream = nullptr;    // the caller's stream; pipeline 0 runs on it
     static constexpr int kMaxPipes = 32;
     int npipes = 1;
@@ -185,6 +197,12 @@ private:
     bool cache_valid = false;        // is_first_intersection_cached (Renderer.cpp:580)
     bool external_image = false;
     float* ext_image = nullptr;
+    bool moments_on = false;         // enableMoments: every pipeline has a contribution buffer, k_merge_m2 merges
+    float* ext_m2 = nullptr;         // the caller's moment buffer (null: allocated here)
+    float* m2 = nullptr;             // W*H*3 sums of squared contributions
+    double* noise_sum = nullptr;     // noise(): per-tile sums, then the mean
+    float* noise_err = nullptr;      // per-tile errors, then the largest
+    int samples_accumulated = 0;     // iterations enqueued since allocateOnGPU / clearImage
     int profiling = 0;
     std::vector<void*> allocs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> bounce_events, first_events, scan_events, trace_events, sort_events;

@@ -3178,7 +3178,7 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     for (int i = 0; i < npipes; i++) {
         pk[i] = kp;
         if (allocPipe(pk[i], cap, stream) != 0) return -1;
-        if (npipes > 1) {
+        if (npipes > 1 || moments_on) {     // moments: a single pipeline merges through k_merge_m2 too
             PT_HIP(upload(allocs, &pk[i].contrib, nullptr, (size_t)npix_all * 3 * sizeof(float), stream));
             PT_HIP(hipMemsetAsync(pk[i].contrib, 0, (size_t)npix_all * 3 * sizeof(float), stream));
         }
@@ -3186,6 +3186,7 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     }
     if (!fork_ev) PT_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
     kp = pk[0];
+    if (moments_on && allocMoments() != 0) return -1;
     PT_HIP(hipStreamSynchronize(stream));
     const char* gr = std::getenv("PT_GRAPH");
     use_graph = gr && std::atoi(gr) != 0;
@@ -3245,6 +3246,11 @@ int Renderer::clearImage() {
     const size_t n = (size_t)cfg.width * cfg.height * 3;
     hipLaunchKernelGGL(k_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, kp.image, n);
     PT_HIP(hipGetLastError());
+    if (moments_on) {
+        hipLaunchKernelGGL(k_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m2, n);
+        PT_HIP(hipGetLastError());
+    }
+    samples_accumulated = 0;
     // a fault invalidated the image it was counted against; the cleared image starts
     // a new render, so later checks report only faults of renders after this point
     PT_HIP(hipMemsetAsync(kp.segments + kTraceFaultCounter, 0, sizeof(unsigned long long), stream));
@@ -3403,7 +3409,7 @@ void Renderer::dropGraphs() {
 int Renderer::renderLoop(int first_iter, int n_iters) {
     if (!allocated) { last_error = "renderLoop before allocateOnGPU"; return -1; }
     if (n_iters < 0 || first_iter < 0) { last_error = "bad iteration range"; return -1; }
-    if (kp.npix == 0) return 0;
+    if (kp.npix == 0) { samples_accumulated += n_iters; return 0; }
     if (!kp.image || !kp.cache_hit || !kp.models) { last_error = "renderLoop: device buffers missing"; return -1; }
     if (!cache_valid) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -3457,9 +3463,17 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
         if (np > 1) {
             // image += this iteration's contributions, after the previous iteration's merge
             if (it > 0) PT_HIP(hipStreamWaitEvent(st, merge_ev[(it - 1) % np], 0));
-            hipLaunchKernelGGL(k_merge, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, k.image, k.contrib, n3);
-            PT_HIP(hipGetLastError());
+            if (moments_on) {
+                if (launchMergeM2(k, st) != 0) return -1;    // ... and m2 += their squares, in the same pass
+            } else {
+                hipLaunchKernelGGL(k_merge, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, k.image, k.contrib, n3);
+                PT_HIP(hipGetLastError());
+            }
             PT_HIP(hipEventRecord(merge_ev[q], st));
+        } else if (moments_on) {
+            // one pipeline: k_bounce wrote the contribution buffer instead of the image;
+            // the same single add per pixel, on the same stream
+            if (launchMergeM2(k, st) != 0) return -1;
         }
         return 0;
     };
@@ -3468,6 +3482,7 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
     for (; done < n_iters; done++) {
         if ((rc = body(done)) != 0) break;
     }
+    samples_accumulated += done;
     const std::string err = last_error;
     const int jrc = joinPipes(np);
     if (rc != 0) { last_error = err; return -1; }     // the first failure is the one reported
@@ -3802,6 +3817,9 @@ void Renderer::freeBuffers() {
     for (void* p : allocs) hipFree(p);
     allocs.clear();
     kp.image = nullptr;
+    m2 = nullptr;
+    noise_sum = nullptr;
+    noise_err = nullptr;
     allocated = false;
     cache_valid = false;
 }

@@ -7,6 +7,10 @@ own float3 accumulator and one all-reduce (sum) combines them.  The
 all-reduce runs whenever a process group exists, at world size 1 too, so a
 one-rank RCCL group exercises the same ordering (the collective on the torch
 stream after the renderer's launches) as the 8-GPU run.
+
+Sums of squared contributions add over iteration shards like the image, so
+``moments=True`` all-reduces a second buffer and evaluates the noise estimate
+on the reduced pair.
 """
 from __future__ import annotations
 
@@ -23,13 +27,20 @@ def shard_iterations(total: int, rank: int, world: int) -> tuple[int, int]:
 
 
 def render_sharded(scene, cfg, total_iters: int, device=None,
-                   render_fn: Optional[Callable] = None):
+                   render_fn: Optional[Callable] = None, moments: bool = False):
     """Render ``total_iters`` samples per pixel across the process group and
     return the summed accumulator (a (W*H*3,) float32 tensor on every rank).
 
     ``render_fn(first, n, image_tensor)`` may replace the GPU renderer (used
     by the CPU tests with the oracle); by default the gfx950 Renderer renders
     straight into ``image_tensor`` on the current stream.
+
+    ``moments=True`` also accumulates the per-pixel sums of squared
+    contributions (Renderer.enable_moments) in a second tensor, all-reduces it
+    beside the image and returns ``(image, m2, noise)``: ``noise`` is
+    ``Renderer.noise(total_iters)`` on the reduced buffers.  ``render_fn`` is
+    then called as ``render_fn(first, n, image_tensor, m2_tensor)`` and
+    ``noise`` is None.
     """
     import torch
     import torch.distributed as dist
@@ -41,18 +52,29 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if render_fn is None else torch.device("cpu")
     image = torch.zeros(cfg.width * cfg.height * 3, dtype=torch.float32, device=device)
+    m2 = torch.zeros_like(image) if moments else None
     if render_fn is not None:
-        render_fn(first, n, image)
+        if moments:
+            render_fn(first, n, image, m2)
+        else:
+            render_fn(first, n, image)
     else:
         from . import Renderer
         r = Renderer(cfg)
         r.set_stream(torch.cuda.current_stream(device).cuda_stream)
         r.bind_image(image.data_ptr(), keepalive=image)
+        if moments:
+            r.enable_moments(m2.data_ptr(), keepalive=m2)
         r.allocateOnGPU(scene)
         r.renderLoop(first_iter=first, n_iters=n, sync=False)
     if grouped:
         dist.all_reduce(image, op=dist.ReduceOp.SUM)      # RCCL (nccl backend) over xGMI, or gloo
+        if moments:
+            dist.all_reduce(m2, op=dist.ReduceOp.SUM)
+    noise = None
     if render_fn is None:
         torch.cuda.synchronize(device)
+        if moments:
+            noise = r.noise(total_iters)      # on the reduced image and moments, before they are unbound
         r.free()
-    return image
+    return (image, m2, noise) if moments else image
