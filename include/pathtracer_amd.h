@@ -234,6 +234,70 @@ int pt_renderer_noise(pt_renderer *r, int samples, double *mean_err, float *max_
  * reference. */
 int pt_renderer_render_until(pt_renderer *r, int first_iter, int min_iters, int max_iters,
                              int check_every, double target, int *iters_done, double *mean_err);
+
+/* ---- Variance-guided edge-avoiding denoiser of the accumulated image (an a-trous
+ * filter in the style of SVGF's spatial pass; no counterpart in the reference, which
+ * writes the raw mean).  Needs pt_renderer_enable_moments.  A render that never calls it
+ * allocates, launches and computes exactly what it did: the filter's buffers (56 bytes
+ * per pixel) are allocated by the first call and freed with the renderer. ---- */
+#define PT_DENOISE_MAX_PASSES 6
+typedef struct pt_denoise_params {
+    int passes;               /* a-trous passes, 1..PT_DENOISE_MAX_PASSES (default 5): pass s has taps 1 << s apart */
+    float sigma_l, sigma_z;   /* luminance and depth stopping widths, finite and > 0 (defaults 4.0, 1.0) */
+} pt_denoise_params;
+void pt_default_denoise_params(pt_denoise_params *p);
+/* Filters the mean image S / nf, guided by the variance of the mean from S = image and
+ * Q = moments and by the primary-hit cache (depth d, world normal n, model k; the same
+ * for every iteration: camera rays carry no jitter).  nf = (float)samples, resolved as in
+ * pt_renderer_noise (samples <= 0: the sample count; fewer than 2 is refused with "need
+ * at least 2 samples").  All arithmetic is float32 IEEE add, multiply, divide and square
+ * root, in exactly this order; pixel index p = y*W + x.
+ * Prep, per pixel:
+ *   for k in r,g,b:  m_k = S_k / nf;  q = Q_k / nf;  v = q - m_k*m_k;  v = v > 0 ? v : 0;
+ *                    v_k = v / (nf - 1.0f);
+ *   c = (m_r, m_g, m_b);  V = (v_r + v_g) + v_b;
+ *   pixels dropped by tail_drop (index >= the traced count) get k = -1, d = FLT_MAX like a miss;
+ *   slope g = max(|d[y][x+] - d[y][x-]| * 0.5f, |d[y+][x] - d[y-][x]| * 0.5f), x+- = clamp(x +- 1,
+ *   0, W-1), y+- = clamp(y +- 1, 0, H-1), whatever the neighbours' models.
+ * Pass s = 0 .. passes-1, step = 1 << s, reads (c, V) of the previous pass and writes new ones.
+ * H5 = {1/16, 1/4, 3/8, 1/4, 1/16}, G3 = {1/4, 1/2, 1/4}.  A pixel with k_p < 0 (miss or
+ * dropped) copies its c and V in every pass and contributes to no other pixel.  Otherwise:
+ *   Vbar = sum over j = -1..1 (outer), i = -1..1 of (G3[j+1]*G3[i+1]) * V[clamp(y+j)][clamp(x+i)],
+ *          from 0.0f, any model;
+ *   L_p = (c_r + c_g) + c_b;  den_l = sigma_l * sqrtf(Vbar) + 1e-4f;  sw = sc[3] = sv = 0;
+ *   for j = -2..2 (outer), i = -2..2, tap q = (x + i*step, y + j*step), skipped when outside the
+ *   frame or k_q != k_p:
+ *     centre (i == 0 && j == 0):  w = H5[2]*H5[2];
+ *     else  dot = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  wn = dot > 0 ? dot : 0;
+ *           wn = wn*wn, six times;  r = (float)(step * (|i| + |j|));
+ *           a = (d_q - d_p) / (sigma_z * (g_p * r + 1e-3f * d_p));  wz = 1.0f / (1.0f + a*a);
+ *           xl = (L_q - L_p) / den_l;  wl = 1.0f / (1.0f + xl*xl);
+ *           w = (H5[j+2]*H5[i+2]) * ((wn * wz) * wl);
+ *     sw += w;  sc[k] += w * c_q[k];  sv += (w*w) * V_q;
+ *   c[k] = sc[k] / sw;  V = sv / (sw*sw).            (sw >= 9/64)
+ * The result is the last pass's c (host_rgb, W*H*3 floats, may be NULL; device_rgb_out, W*H*3
+ * floats of device memory, NULL: the result stays in the renderer's own buffer) and V (host_var,
+ * W*H floats, may be NULL).  p = NULL: the defaults.  The image and the moments are not modified.
+ * Runs on the renderer's stream, synchronizes, and fails like pt_renderer_read_image after a
+ * trace fault.  No atomics: a call repeats bit for bit.  Passes with step <= PT_DENOISE_LDS
+ * (environment, read at every call: 0, 1, 2, 4 or 8; default 4) stage their tile in LDS, the
+ * others read their taps from global memory; the results are the same for every value
+ * (another value is refused: "PT_DENOISE_LDS must be 0, 1, 2, 4 or 8").
+ * Refused before any launch: null renderer, "not allocated", "moments not enabled", "need at
+ * least 2 samples", "bad denoise parameters" (passes outside 1..6, a sigma not finite and > 0).
+ * Limits: it filters the accumulator's sqrt(color) space; inside one model only the luminance
+ * term stops at reflections; silhouette pixels have a large slope and so little depth stopping.
+ * No counterpart in the reference. */
+int pt_renderer_denoise(pt_renderer *r, int samples, const pt_denoise_params *p,
+                        float *device_rgb_out, float *host_rgb, float *host_var);
+/* pt_renderer_denoise, then the BMP of the denoised mean D with pt_renderer_render_image's
+ * conversion: bytes (int)(D * 255.0f) & 0xFF, rows bottom-up.  No counterpart in the reference. */
+int pt_renderer_render_image_denoised(pt_renderer *r, const char *bmp_path, int samples,
+                                      const pt_denoise_params *p);
+/* HIP-event times in ms of the last pt_renderer_denoise made with pt_renderer_set_profiling
+ * on: ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy into device_rgb_out,
+ * ms[8] first kernel to last; n values (0 beyond 9).  No counterpart in the reference. */
+int pt_renderer_denoise_times(pt_renderer *r, double *ms, int n);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

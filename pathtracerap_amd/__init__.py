@@ -33,6 +33,7 @@ ACCEL_GRID = 0
 ACCEL_BVH = 1
 ACCEL_GRID_FAST = 2
 NOISE_TILE = 16     # PT_NOISE_TILE: Renderer.noise()'s tile edge in pixels
+DENOISE_MAX_PASSES = 6     # PT_DENOISE_MAX_PASSES
 # renderer.h: segments[] slots after the per-bounce counters, as segments_per_bounce indices
 _MAX_BOUNCE_COUNTERS = 64
 _DEFERRED_SLOT = 50 + _MAX_BOUNCE_COUNTERS - 1     # kDeferredRayCounter
@@ -63,6 +64,10 @@ class _Cfg(ctypes.Structure):
         ("plane_w", ctypes.c_double), ("plane_h", ctypes.c_double), ("block", ctypes.c_int),
         ("pipelines", ctypes.c_int), ("ray_sort", ctypes.c_int),
     ]
+
+
+class _DenoiseParams(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int), ("sigma_l", ctypes.c_float), ("sigma_z", ctypes.c_float)]
 
 
 _P_F = ctypes.POINTER(ctypes.c_float)
@@ -116,6 +121,12 @@ EXPORTS = [
     ("pt_renderer_noise", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _P_F, _P_F]),
     ("pt_renderer_render_until", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_double, _P_I, ctypes.POINTER(ctypes.c_double)]),
+    ("pt_default_denoise_params", None, [ctypes.POINTER(_DenoiseParams)]),
+    ("pt_renderer_denoise", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_DenoiseParams), ctypes.c_void_p,
+                                           _P_F, _P_F]),
+    ("pt_renderer_render_image_denoised", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int,
+                                                         ctypes.POINTER(_DenoiseParams)]),
+    ("pt_renderer_denoise_times", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -331,6 +342,7 @@ class Renderer:
             _err(-1, "pt_renderer_create")
         self._image_ref = None
         self._m2_ref = None
+        self._denoise_ref = None
 
     def set_stream(self, hip_stream: int) -> None:
         _err(lib().pt_renderer_set_stream(self._h, ctypes.c_void_p(int(hip_stream))), "set_stream")
@@ -474,6 +486,39 @@ class Renderer:
         rc = _err(lib().pt_renderer_render_until(self._h, int(first_iter), int(min_iters), int(max_iters), int(check_every),
                                                  float(target), ctypes.byref(done), ctypes.byref(mean)), "render_until")
         return bool(rc), done.value, mean.value
+
+    def denoise(self, samples: int | None = None, passes: int = 5, sigma_l: float = 4.0, sigma_z: float = 1.0,
+                out_ptr: int | None = None, keepalive=None, variance: bool = False):
+        """Variance-guided edge-avoiding filter of the accumulated mean image
+        (include/pathtracer_amd.h, pt_renderer_denoise; needs enable_moments) -> the
+        denoised (W*H, 3) float32 image, with ``variance=True`` (image, var (W*H,)).
+        ``samples``: None = the iterations rendered since allocateOnGPU / clearImage (a
+        caller who reduced shards into bound tensors passes the total).  ``out_ptr``: a
+        caller-owned W*H*3 float device buffer (a torch tensor, kept alive by
+        ``keepalive``) that receives the image too.  The image and the moments are not
+        modified."""
+        self._denoise_ref = keepalive
+        p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
+        img = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
+        var = np.zeros(self.cfg.width * self.cfg.height, np.float32) if variance else None
+        _err(lib().pt_renderer_denoise(self._h, int(samples or 0), ctypes.byref(p),
+                                       ctypes.c_void_p(int(out_ptr)) if out_ptr else None, _fp(img),
+                                       _fp(var) if variance else None), "denoise")
+        return (img, var) if variance else img
+
+    def renderImageDenoised(self, path: str = "Render.bmp", samples: int | None = None, passes: int = 5,
+                            sigma_l: float = 4.0, sigma_z: float = 1.0) -> None:
+        """The BMP of the denoised mean (renderImage's conversion of D * 255)."""
+        p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
+        _err(lib().pt_renderer_render_image_denoised(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p)),
+             "renderImageDenoised")
+
+    def denoise_times(self) -> dict:
+        """HIP-event times (ms) of the last denoise() made with set_profiling on: ``prep``,
+        ``passes`` (one per pass run), ``out`` (the copy into ``out_ptr``) and ``total``."""
+        ms = (ctypes.c_double * 9)()
+        _err(lib().pt_renderer_denoise_times(self._h, ms, 9), "denoise_times")
+        return dict(prep=ms[0], passes=[ms[1 + i] for i in range(DENOISE_MAX_PASSES)], out=ms[7], total=ms[8])
 
     def free(self) -> None:
         if self._h:

@@ -328,6 +328,30 @@ int pt_renderer_render_until(pt_renderer* r, int first_iter, int min_iters, int 
                              double target, int* iters_done, double* mean_err) {
     R_CALL(r->r->renderUntil(first_iter, min_iters, max_iters, check_every, target, iters_done, mean_err));
 }
+void pt_default_denoise_params(pt_denoise_params* p) {
+    if (!p) return;
+    p->passes = 5;
+    p->sigma_l = 4.0f;
+    p->sigma_z = 1.0f;
+}
+int pt_renderer_denoise(pt_renderer* r, int samples, const pt_denoise_params* p, float* device_rgb_out, float* host_rgb,
+                        float* host_var) {
+    pt_denoise_params d;
+    pt_default_denoise_params(&d);
+    if (p) d = *p;
+    R_CALL(r->r->denoise(samples, d.passes, d.sigma_l, d.sigma_z, device_rgb_out, host_rgb, host_var));
+}
+int pt_renderer_render_image_denoised(pt_renderer* r, const char* path, int samples, const pt_denoise_params* p) {
+    if (!path) return set_err("bad arguments");
+    pt_denoise_params d;
+    pt_default_denoise_params(&d);
+    if (p) d = *p;
+    R_CALL(r->r->renderImageDenoised(path, samples, d.passes, d.sigma_l, d.sigma_z));
+}
+int pt_renderer_denoise_times(pt_renderer* r, double* ms, int n) {
+    if (!ms || n < 0) return set_err("bad arguments");
+    R_CALL(r->r->denoiseTimes(ms, n));
+}
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;

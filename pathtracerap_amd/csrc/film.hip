@@ -1,5 +1,6 @@
-// film.hip -- per-pixel second moment, noise estimate and render-until-converged
-// (no counterpart in the reference, which renders a fixed ITER samples).
+// film.hip -- per-pixel second moment, noise estimate, render-until-converged and
+// the variance-guided edge-avoiding denoiser (no counterpart in the reference, which
+// renders a fixed ITER samples and writes the raw mean).
 //
 // Every pixel receives one contribution c = sqrt(color) per iteration.  With
 // moments on, every pipeline (a single one too) writes c to its contribution
@@ -13,7 +14,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/pathtracer_amd.h"
 #include "renderer.h"
@@ -127,6 +132,205 @@ __global__ __launch_bounds__(256) void k_noise_final(const double* __restrict__ 
     if (threadIdx.x == 0) {
         *out_mean = t / npix;
         *out_max = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Denoiser: an a-trous filter in the style of SVGF's spatial pass, guided by the
+// per-pixel variance of the mean (from S and Q) and by the primary-hit cache
+// (depth, world normal, model).  include/pathtracer_amd.h (pt_renderer_denoise)
+// states the arithmetic; the kernels keep its float32 operations and their order
+// (IEEE add, multiply, divide, square root; -ffp-contract=off), so the result
+// equals the numpy restatement in tests/denoise_ref.py bit for bit.
+//
+// Per-pixel records, built once per call by k_denoise_prep: (c.rgb, V) ping-pong,
+// (n.xyz, d), the model and the depth slope.  No atomics: a call repeats bit for bit.
+// ---------------------------------------------------------------------------
+__device__ inline float dn_h5(int i) { return i == 2 ? 0.375f : ((i == 1) | (i == 3)) ? 0.25f : 0.0625f; }
+__device__ inline float dn_g3(int i) { return i == 1 ? 0.5f : 0.25f; }
+__device__ inline int dn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// depth of frame pixel idx in the primary-hit cache; pixels tail_drop left out count as misses
+__device__ inline float dn_depth(const float4* __restrict__ cache_hit, int npix, size_t idx) {
+    return idx < (size_t)npix ? cache_hit[idx].x : FLT_MAX;
+}
+
+// One pixel's records from its sums s, q (3 floats each).
+__device__ inline void dn_prep_pixel(size_t p, const float* s, const float* q, float nf,
+                                     const float4* __restrict__ cache_hit, const int* __restrict__ cache_model, int npix,
+                                     int W, int H, float4* __restrict__ cv, float4* __restrict__ nd,
+                                     int* __restrict__ model, float* __restrict__ slope) {
+    float m[3], v[3];
+    for (int k = 0; k < 3; k++) {
+        m[k] = s[k] / nf;
+        const float qq = q[k] / nf;
+        float t = qq - m[k] * m[k];
+        t = t > 0.0f ? t : 0.0f;
+        v[k] = t / (nf - 1.0f);
+    }
+    cv[p] = make_float4(m[0], m[1], m[2], (v[0] + v[1]) + v[2]);
+    const bool live = p < (size_t)npix;
+    const float4 h = live ? cache_hit[p] : make_float4(FLT_MAX, 0.0f, 0.0f, 0.0f);
+    nd[p] = make_float4(h.y, h.z, h.w, h.x);
+    model[p] = live ? cache_model[p] : -1;
+    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+    const int xm = dn_clamp(x - 1, W - 1), xp = dn_clamp(x + 1, W - 1);
+    const int ym = dn_clamp(y - 1, H - 1), yp = dn_clamp(y + 1, H - 1);
+    const float gx = fabsf(dn_depth(cache_hit, npix, (size_t)y * W + xp) - dn_depth(cache_hit, npix, (size_t)y * W + xm)) * 0.5f;
+    const float gy = fabsf(dn_depth(cache_hit, npix, (size_t)yp * W + x) - dn_depth(cache_hit, npix, (size_t)ym * W + x)) * 0.5f;
+    slope[p] = gx > gy ? gx : gy;
+}
+
+// VEC: a lane takes 4 pixels = 3 float4 of S and of Q (16-byte aligned S and Q; the last
+// npixels % 4 pixels go one per lane); otherwise one pixel per lane, scalar reads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_denoise_prep(const float* __restrict__ S, const float* __restrict__ Q, float nf,
+                                                      const float4* __restrict__ cache_hit,
+                                                      const int* __restrict__ cache_model, int npix, int W, int H,
+                                                      float4* __restrict__ cv, float4* __restrict__ nd,
+                                                      int* __restrict__ model, float* __restrict__ slope) {
+    const size_t n = (size_t)W * H;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const size_t n4 = n >> 2;
+        if (i < n4) {
+            float s[12], q[12];
+            for (int k = 0; k < 3; k++) {
+                const float4 a = reinterpret_cast<const float4*>(S)[3 * i + k];
+                const float4 b = reinterpret_cast<const float4*>(Q)[3 * i + k];
+                s[4 * k] = a.x; s[4 * k + 1] = a.y; s[4 * k + 2] = a.z; s[4 * k + 3] = a.w;
+                q[4 * k] = b.x; q[4 * k + 1] = b.y; q[4 * k + 2] = b.z; q[4 * k + 3] = b.w;
+            }
+            for (int k = 0; k < 4; k++)
+                dn_prep_pixel(4 * i + k, s + 3 * k, q + 3 * k, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+        }
+        if (i < (n & 3)) {
+            const size_t p = (n4 << 2) + i;
+            const float s[3] = {S[3 * p], S[3 * p + 1], S[3 * p + 2]};
+            const float q[3] = {Q[3 * p], Q[3 * p + 1], Q[3 * p + 2]};
+            dn_prep_pixel(p, s, q, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+        }
+    } else if (i < n) {
+        const float s[3] = {S[3 * i], S[3 * i + 1], S[3 * i + 2]};
+        const float q[3] = {Q[3 * i], Q[3 * i + 1], Q[3 * i + 2]};
+        dn_prep_pixel(i, s, q, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+    }
+}
+
+// The staged image of a pass: the 16 x 16 tile and its 2 * STEP halo.  Rows of the
+// float4 planes are padded to a multiple of 16 records (256 B = every bank once): a
+// ds_read_b128 lane group spans two tile rows, whose 16 x positions then fall on 16
+// different 16-byte bank groups.  The model plane (ds_read_b32, 32 banks, a lane group
+// = two tile rows) has rows of 48 words, so the second row lands 16 banks on.
+template <int STEP>
+struct DnTile {
+    static constexpr int kHalo = 2 * STEP;
+    static constexpr int kEdge = kTile + 2 * kHalo;             // 20, 24, 32, 48
+    static constexpr int kRow = (kEdge + 15) / 16 * 16;         // 32, 32, 32, 48
+    static constexpr int kRowM = 48;
+    static_assert(kEdge <= kRowM, "the staged variant stops at step 8");
+};
+
+// One a-trous pass with taps STEP apart: reads (c, V) of the previous pass, writes the
+// next.  One workgroup per 16 x 16 tile (edge tiles partial), one lane per pixel.
+// STAGE: the tile's records and their halo go through LDS (positions outside the frame
+// carry model -2, which equals no pixel's model); otherwise the 25 taps are read from
+// global memory.  Both variants evaluate the same expressions in the same order.
+template <int STEP, bool STAGE>
+__global__ __launch_bounds__(kTileWG) void k_denoise_pass(const float4* __restrict__ cv_in, float4* __restrict__ cv_out,
+                                                          const float4* __restrict__ nd, const int* __restrict__ model,
+                                                          const float* __restrict__ slope, int W, int H, int tiles_x,
+                                                          float sigma_l, float sigma_z) {
+    using T = DnTile<STAGE ? STEP : 1>;
+    __shared__ float4 s_cv[STAGE ? T::kEdge * T::kRow : 1];
+    __shared__ float4 s_nd[STAGE ? T::kEdge * T::kRow : 1];
+    __shared__ int s_k[STAGE ? T::kEdge * T::kRowM : 1];
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int x = tx * kTile + (threadIdx.x % kTile), y = ty * kTile + (threadIdx.x / kTile);
+    const int x0 = tx * kTile - T::kHalo, y0 = ty * kTile - T::kHalo;    // frame position of the staged image's corner
+    if (STAGE) {
+        for (int idx = threadIdx.x; idx < T::kEdge * T::kEdge; idx += kTileWG) {
+            const int sy = idx / T::kEdge, sx = idx - sy * T::kEdge;
+            const int gx = x0 + sx, gy = y0 + sy;
+            int k = -2;
+            if ((gx >= 0) & (gx < W) & (gy >= 0) & (gy < H)) {
+                const size_t g = (size_t)gy * W + gx;
+                k = model[g];
+                s_cv[sy * T::kRow + sx] = cv_in[g];
+                s_nd[sy * T::kRow + sx] = nd[g];
+            }
+            s_k[sy * T::kRowM + sx] = k;
+        }
+        __syncthreads();
+    }
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    // records of frame position (qx, qy): inside the staged image for every tap and every
+    // clamped 3 x 3 neighbour of a tile pixel
+    auto rec_cv = [&](int qx, int qy) { return STAGE ? s_cv[(qy - y0) * T::kRow + (qx - x0)] : cv_in[(size_t)qy * W + qx]; };
+    auto rec_nd = [&](int qx, int qy) { return STAGE ? s_nd[(qy - y0) * T::kRow + (qx - x0)] : nd[(size_t)qy * W + qx]; };
+    const int kp = STAGE ? s_k[(y - y0) * T::kRowM + (x - x0)] : model[p];
+    const float4 cp = rec_cv(x, y);
+    if (kp < 0) {                            // miss or dropped: passes through, contributes nowhere
+        cv_out[p] = cp;
+        return;
+    }
+    float vbar = 0.0f;
+#pragma unroll
+    for (int j = -1; j <= 1; j++)
+#pragma unroll
+        for (int i = -1; i <= 1; i++)
+            vbar += (dn_g3(j + 1) * dn_g3(i + 1)) * rec_cv(dn_clamp(x + i, W - 1), dn_clamp(y + j, H - 1)).w;
+    const float4 np4 = rec_nd(x, y);
+    const float dp = np4.w, gp = slope[p];
+    const float lp = (cp.x + cp.y) + cp.z;
+    const float den_l = sigma_l * sqrtf(vbar) + 1e-4f;
+    float sw = 0.0f, sc0 = 0.0f, sc1 = 0.0f, sc2 = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int j = -2; j <= 2; j++) {
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qx = x + i * STEP, qy = y + j * STEP;
+            int kq;
+            if (STAGE) {
+                kq = s_k[(qy - y0) * T::kRowM + (qx - x0)];
+            } else {
+                if ((qx < 0) | (qx >= W) | (qy < 0) | (qy >= H)) continue;
+                kq = model[(size_t)qy * W + qx];
+            }
+            if (kq != kp) continue;
+            const float4 cq = rec_cv(qx, qy);
+            float w;
+            if (i == 0 && j == 0) {
+                w = dn_h5(2) * dn_h5(2);
+            } else {
+                const float4 nq = rec_nd(qx, qy);
+                const float dot = (np4.x * nq.x + np4.y * nq.y) + np4.z * nq.z;
+                float wn = dot > 0.0f ? dot : 0.0f;
+                wn = wn * wn; wn = wn * wn; wn = wn * wn; wn = wn * wn; wn = wn * wn; wn = wn * wn;
+                const float r = (float)(STEP * ((i < 0 ? -i : i) + (j < 0 ? -j : j)));
+                const float a = (nq.w - dp) / (sigma_z * (gp * r + 1e-3f * dp));
+                const float wz = 1.0f / (1.0f + a * a);
+                const float xl = (((cq.x + cq.y) + cq.z) - lp) / den_l;
+                const float wl = 1.0f / (1.0f + xl * xl);
+                w = (dn_h5(j + 2) * dn_h5(i + 2)) * ((wn * wz) * wl);
+            }
+            sw += w;
+            sc0 += w * cq.x;
+            sc1 += w * cq.y;
+            sc2 += w * cq.z;
+            sv += (w * w) * cq.w;
+        }
+    }
+    cv_out[p] = make_float4(sc0 / sw, sc1 / sw, sc2 / sw, sv / (sw * sw));
+}
+
+// The packed result as W*H*3 floats in the caller's (or another) device buffer.
+__global__ __launch_bounds__(256) void k_denoise_out(const float4* __restrict__ cv, size_t n, float* __restrict__ rgb) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const float4 c = cv[i];
+        rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
     }
 }
 
@@ -247,6 +451,150 @@ int Renderer::renderUntil(int first_iter, int min_iters, int max_iters, int chec
     if (iters_done) *iters_done = done;
     if (mean_err) *mean_err = mean;
     return converged;
+}
+
+// The denoiser's records, on the first denoise call: 56 bytes per pixel, freed with
+// the renderer's other buffers.
+int Renderer::allocDenoise() {
+    if (dn_cv[0]) return 0;
+    const size_t n = (size_t)cfg.width * cfg.height;
+    void* d[5] = {};
+    const size_t bytes[5] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float4), n * sizeof(int), n * sizeof(float)};
+    for (int i = 0; i < 5; i++) {
+        PT_HIP(hipMalloc(&d[i], bytes[i]));
+        allocs.push_back(d[i]);
+    }
+    dn_cv[1] = (float4*)d[1];
+    dn_nd = (float4*)d[2];
+    dn_model = (int*)d[3];
+    dn_slope = (float*)d[4];
+    dn_cv[0] = (float4*)d[0];
+    return 0;
+}
+
+template <int STEP>
+static void launchDenoisePass(bool stage, dim3 grid, hipStream_t st, const float4* in, float4* out, const float4* nd,
+                              const int* model, const float* slope, int W, int H, int tiles_x, float sl, float sz) {
+    if (stage) hipLaunchKernelGGL((k_denoise_pass<STEP, true>), grid, dim3(kTileWG), 0, st, in, out, nd, model, slope, W, H, tiles_x, sl, sz);
+    else hipLaunchKernelGGL((k_denoise_pass<STEP, false>), grid, dim3(kTileWG), 0, st, in, out, nd, model, slope, W, H, tiles_x, sl, sz);
+}
+
+int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, float* device_rgb_out, float* host_rgb,
+                      float* host_var) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!moments_on) { last_error = "moments not enabled"; return -1; }
+    if (samples <= 0) samples = samples_accumulated;
+    if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
+    if (passes < 1 || passes > PT_DENOISE_MAX_PASSES || !std::isfinite(sigma_l) || !(sigma_l > 0.0f) ||
+        !std::isfinite(sigma_z) || !(sigma_z > 0.0f)) {
+        last_error = "bad denoise parameters";
+        return -1;
+    }
+    // the largest step whose pass stages its tile in LDS (0: none); results are the same for every value
+    int lds_step = kDenoiseLdsDefault;
+    if (const char* e = std::getenv("PT_DENOISE_LDS")) {
+        lds_step = std::atoi(e);
+        if (lds_step != 0 && lds_step != 1 && lds_step != 2 && lds_step != 4 && lds_step != 8) {
+            last_error = "PT_DENOISE_LDS must be 0, 1, 2, 4 or 8";
+            return -1;
+        }
+    }
+    if (allocDenoise() != 0) return -1;
+    if (!cache_valid && launchPrimary() != 0) return -1;
+    const int W = cfg.width, H = cfg.height;
+    const size_t n = (size_t)W * H;
+    // HIP events around every kernel when profiling is on (denoiseTimes)
+    for (hipEvent_t ev : dn_events) hipEventDestroy(ev);
+    dn_events.clear();
+    dn_event_passes = 0;
+    const bool timed = profiling != 0;
+    auto mark = [&]() -> int {
+        if (!timed) return 0;
+        hipEvent_t ev;
+        PT_HIP(hipEventCreate(&ev));
+        dn_events.push_back(ev);
+        PT_HIP(hipEventRecord(ev, stream));
+        return 0;
+    };
+    if (mark() != 0) return -1;
+    const bool vec = (((uintptr_t)kp.image | (uintptr_t)m2) & 15) == 0;
+    if (vec) {
+        const size_t n4 = n >> 2;
+        hipLaunchKernelGGL(k_denoise_prep<true>, dim3((unsigned)std::max<size_t>(1, (n4 + 255) / 256)), dim3(256), 0, stream,
+                           kp.image, m2, (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd,
+                           dn_model, dn_slope);
+    } else {
+        hipLaunchKernelGGL(k_denoise_prep<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                           kp.image, m2, (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd,
+                           dn_model, dn_slope);
+    }
+    PT_HIP(hipGetLastError());
+    if (mark() != 0) return -1;
+    const int tx = noiseTilesX();
+    const dim3 grid((unsigned)(tx * noiseTilesY()));
+    for (int s = 0; s < passes; s++) {
+        const float4* in = dn_cv[s & 1];
+        float4* out = dn_cv[(s + 1) & 1];
+        const int step = 1 << s;
+        const bool stage = step <= lds_step;
+        switch (step) {
+            case 1: launchDenoisePass<1>(stage, grid, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+            case 2: launchDenoisePass<2>(stage, grid, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+            case 4: launchDenoisePass<4>(stage, grid, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+            case 8: launchDenoisePass<8>(stage, grid, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+            case 16: hipLaunchKernelGGL((k_denoise_pass<16, false>), grid, dim3(kTileWG), 0, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+            default: hipLaunchKernelGGL((k_denoise_pass<32, false>), grid, dim3(kTileWG), 0, stream, in, out, dn_nd, dn_model, dn_slope, W, H, tx, sigma_l, sigma_z); break;
+        }
+        PT_HIP(hipGetLastError());
+        if (mark() != 0) return -1;
+    }
+    dn_event_passes = timed ? passes : 0;
+    const float4* result = dn_cv[passes & 1];
+    if (device_rgb_out) {
+        hipLaunchKernelGGL(k_denoise_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, result, n, device_rgb_out);
+        PT_HIP(hipGetLastError());
+    }
+    if (mark() != 0) return -1;
+    std::vector<float4> host;
+    if (host_rgb || host_var) {
+        host.resize(n);
+        PT_HIP(hipMemcpyAsync(host.data(), result, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    }
+    PT_HIP(hipStreamSynchronize(stream));
+    if (checkFaults() != 0) return -1;
+    for (size_t i = 0; i < host.size(); i++) {
+        if (host_rgb) { host_rgb[3 * i] = host[i].x; host_rgb[3 * i + 1] = host[i].y; host_rgb[3 * i + 2] = host[i].z; }
+        if (host_var) host_var[i] = host[i].w;
+    }
+    return 0;
+}
+
+// ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy to the caller's device
+// buffer, ms[8] first kernel to last: of the last denoise call made with profiling on.
+int Renderer::denoiseTimes(double* ms, int n) {
+    if (dn_event_passes == 0 || (int)dn_events.size() != dn_event_passes + 3) {
+        last_error = "no timed denoise call (set_profiling, then denoise)";
+        return -1;
+    }
+    double v[9] = {};
+    auto span = [&](int a, int b) {
+        float t = 0.0f;
+        hipEventElapsedTime(&t, dn_events[a], dn_events[b]);
+        return (double)t;
+    };
+    v[0] = span(0, 1);
+    for (int s = 0; s < dn_event_passes; s++) v[1 + s] = span(1 + s, 2 + s);
+    v[7] = span(dn_event_passes + 1, dn_event_passes + 2);
+    v[8] = span(0, dn_event_passes + 2);
+    for (int i = 0; i < n; i++) ms[i] = i < 9 ? v[i] : 0.0;
+    return 0;
+}
+
+// The denoised mean D through renderImage's writer: bytes of D * 255.
+int Renderer::renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z) {
+    std::vector<float> img((size_t)cfg.width * cfg.height * 3);
+    if (denoise(samples, passes, sigma_l, sigma_z, nullptr, img.data(), nullptr) != 0) return -1;
+    return writeBmp(path, img.data(), 1.0f);         // x * 1.0f is x
 }
 
 }  // namespace pt

@@ -2,11 +2,15 @@
 // load a scene, allocate on the GPU, run the render loop, write Render.bmp.
 //
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
-//                  [--pipelines P] [--noise-target X [--check-every N]]
+//                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
 //
 // --noise-target X: render until the mean relative noise estimate (pt_renderer_noise)
 // is at most X, checked every N iterations (default 32); --iter is then the most
 // iterations to render, and the BMP is divided by the iterations actually rendered.
+//
+// --denoise: keep the second moments and write the BMP of the denoised mean
+// (pt_renderer_render_image_denoised over the iterations actually rendered, N a-trous
+// passes, default 5) instead of the raw mean.
 //
 // Default: PT_ACCEL_GRID_FAST (the reference grid's image, bit for bit) with 16
 // iterations in flight, each on its own HIP stream and hardware queue.
@@ -23,7 +27,8 @@ int main(int argc, char** argv) {
     setenv("GPU_MAX_HW_QUEUES", "16", /*overwrite=*/0);
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
-                             "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]]\n", argv[0]);
+                             "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
+                             "[--denoise [--denoise-passes N]]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -34,6 +39,9 @@ int main(int argc, char** argv) {
     const char* out = "Render.bmp";
     double noise_target = -1.0;          // < 0: render cfg.iterations
     int check_every = 32;
+    bool denoise = false;
+    pt_denoise_params dn;
+    pt_default_denoise_params(&dn);
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--res") && i + 2 < argc) { cfg.width = std::atoi(argv[++i]); cfg.height = std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--iter") && i + 1 < argc) cfg.iterations = std::atoi(argv[++i]);
@@ -44,11 +52,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pipelines") && i + 1 < argc) cfg.pipelines = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--noise-target") && i + 1 < argc) noise_target = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--check-every") && i + 1 < argc) check_every = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
     }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
-    if (!r || (noise_target >= 0 && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
+    if (!r || ((noise_target >= 0 || denoise) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }
@@ -68,7 +78,7 @@ int main(int argc, char** argv) {
     double us = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
     long long seg = pt_renderer_segments(r);
     std::printf("Full run: %.0f microseconds, %lld ray segments, %.2f Mrays/s\n", us, seg, seg / us);
-    if (pt_renderer_render_image(r, out, iters) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+    if ((denoise ? pt_renderer_render_image_denoised(r, out, iters, &dn) : pt_renderer_render_image(r, out, iters)) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer_free(r);
     pt_scene_destroy(s);
     return 0;

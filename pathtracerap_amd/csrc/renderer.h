@@ -106,6 +106,8 @@ struct KParams {
                                         // counted in segments[kTraceFaultCounter]); PT_TRACE_ITER_CAP overrides
 };
 
+// denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
+constexpr int kDenoiseLdsDefault = 4;
 constexpr int kMaxBounceCounters = 64;
 constexpr int kDrainLevels = 4;          // most tail launches per trace (drain continuations)
 constexpr int kDiagCounters = 96;        // diagnostic counters after the per-bounce ones (PT_TRACE_STATS builds)
@@ -162,6 +164,12 @@ public:
                     int* iters_done, double* mean_err);
     int noiseTilesX() const { return (cfg.width + 15) / 16; }      // PT_NOISE_TILE
     int noiseTilesY() const { return (cfg.height + 15) / 16; }
+    // film.hip: variance-guided edge-avoiding denoiser of the accumulated image (no counterpart
+    // in the reference); the image and the moments are read only
+    int denoise(int samples, int passes, float sigma_l, float sigma_z, float* device_rgb_out, float* host_rgb,
+                float* host_var);
+    int renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z);
+    int denoiseTimes(double* ms, int n);             // HIP-event times of the last denoise call under setProfiling
 
     RenderConfig cfg;
     std::string last_error;
@@ -180,6 +188,8 @@ private:
     int checkFaults();
     int allocMoments();
     int launchMergeM2(const KParams& k, hipStream_t st);
+    int allocDenoise();
+    int writeBmp(const std::string& path, const float* rgb, float div);     // Renderer.cpp:15-63
 
     KParams kp{};                   // pipeline 0 (and everything the pipelines share)
     hipStream_t stream = nullptr;    // the caller's stream; pipeline 0 runs on it
@@ -203,6 +213,12 @@ private:
     double* noise_sum = nullptr;     // noise(): per-tile sums, then the mean
     float* noise_err = nullptr;      // per-tile errors, then the largest
     int samples_accumulated = 0;     // iterations enqueued since allocateOnGPU / clearImage
+    float4* dn_cv[2] = {};           // denoise(): per pixel (c.rgb, V), ping-pong; allocated by the first call
+    float4* dn_nd = nullptr;         // (n.xyz, d) of the primary hit
+    int* dn_model = nullptr;         // its model (-1: miss or dropped by tail_drop)
+    float* dn_slope = nullptr;       // depth slope
+    std::vector<hipEvent_t> dn_events;   // profiling: around prep, each pass and the output copy
+    int dn_event_passes = 0;
     int profiling = 0;
     std::vector<void*> allocs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> bounce_events, first_events, scan_events, trace_events, sort_events;

@@ -3612,6 +3612,10 @@ int Renderer::readImage(float* host_rgb) {
 int Renderer::renderImage(const std::string& path, int iterations_total) {
     std::vector<float> img((size_t)cfg.width * cfg.height * 3);
     if (readImage(img.data()) != 0) return -1;
+    return writeBmp(path, img.data(), 1 / (float)iterations_total);
+}
+
+int Renderer::writeBmp(const std::string& path, const float* img, float div) {
     const int W = cfg.width, H = cfg.height;
     unsigned char hdr[54] = {'B', 'M', 0, 0, 0, 0, 0, 0, 0, 0, 54, 0, 0, 0, 40, 0, 0, 0};
     std::memcpy(hdr + 18, &W, 4);
@@ -3624,7 +3628,6 @@ int Renderer::renderImage(const std::string& path, int iterations_total) {
     if (!out) { last_error = "cannot open " + path; return -1; }
     out.write((const char*)hdr, 54);
     std::vector<unsigned char> row((size_t)W * 3);
-    const float div = 1 / (float)iterations_total;
     for (int y = 0; y < H; y++) {
         for (int x = 0; x < W; x++)
             for (int k = 0; k < 3; k++) {
@@ -3820,6 +3823,9 @@ void Renderer::freeBuffers() {
     m2 = nullptr;
     noise_sum = nullptr;
     noise_err = nullptr;
+    dn_cv[0] = dn_cv[1] = dn_nd = nullptr;
+    dn_model = nullptr;
+    dn_slope = nullptr;
     allocated = false;
     cache_valid = false;
 }
@@ -3831,6 +3837,9 @@ void Renderer::free() {
     for (auto& ev : scan_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto& ev : trace_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto& ev : sort_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    for (hipEvent_t ev : dn_events) hipEventDestroy(ev);
+    dn_events.clear();
+    dn_event_passes = 0;
     trace_events.clear();
     sort_events.clear();
     bounce_events.clear();
