@@ -298,6 +298,72 @@ int pt_renderer_render_image_denoised(pt_renderer *r, const char *bmp_path, int 
  * on: ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy into device_rgb_out,
  * ms[8] first kernel to last; n values (0 beyond 9).  No counterpart in the reference. */
 int pt_renderer_denoise_times(pt_renderer *r, double *ms, int n);
+
+/* ---- Tile-masked sampling and the adaptive render (added within ABI 9: new functions only;
+ * pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in the reference, which
+ * gives every pixel ITER samples).  Off unless called: a renderer that never calls them
+ * allocates, launches and computes exactly what it did.  Needs pt_renderer_enable_moments.
+ * Tiles are the noise estimate's: PT_NOISE_TILE pixels square, tiles_x = ceil(W/16),
+ * tiles_y = ceil(H/16), row-major, partial in the last column and row. ---- */
+/* Enqueues iterations [first_iter, first_iter + n_iters) that sample only the tiles whose
+ * byte in tile_mask_host (tiles_y * tiles_x bytes) is non-zero; NULL: every tile.  The mask
+ * is copied before the call returns; the upload is ordered on the renderer's stream, so
+ * successive calls with different masks and no synchronize each render under their own.
+ * One masked iteration: at bounce 0 a pixel of an active tile does what it does in
+ * pt_renderer_render_loop (camera ray, cached primary hit, shading with RNG slot = pixel
+ * index, stable compaction); a pixel of an inactive tile emits no ray and contributes 0.0,
+ * which leaves its sum S (image) and Q (moments) bit-identical.  From bounce 1 on a
+ * survivor's slot, the RNG seed, is its rank among the survivors of the active tiles, so
+ * under a partial mask a pixel draws other samples than in a full iteration: equally valid
+ * samples of the same estimator, not the same ones.  With an all-ones mask or NULL the
+ * result equals pt_renderer_render_loop's bit for bit.  Pixels dropped by tail_drop stay
+ * dropped.  A mask with no active tile, or n_iters = 0, enqueues nothing and changes
+ * nothing.  Masked iterations are enqueued directly also under PT_GRAPH=1: they are never
+ * captured or replayed, and the graphs of pt_renderer_render_loop stay valid.
+ * pt_renderer_segments keeps counting the frame's launched pixels as bounce 0's rays of a
+ * masked iteration (the scan that counts them is unchanged); bounces >= 1 count the live
+ * rays.  The sample count of pt_renderer_noise (iterations enqueued) grows by n_iters;
+ * each active tile's count below grows by n_iters.
+ * Errors: not allocated, "moments not enabled ...", "bad iteration range". */
+int pt_renderer_render_loop_masked(pt_renderer *r, int first_iter, int n_iters,
+                                   const unsigned char *tile_mask_host);
+/* Samples per tile since allocate_on_gpu or the last clear_image (tiles_y * tiles_x ints,
+ * may be NULL): pt_renderer_render_loop adds its n to every tile, a masked call to the
+ * active ones.  Returns the tile count.  Once the counts differ between tiles,
+ * pt_renderer_noise, pt_renderer_denoise, pt_renderer_render_image_denoised with
+ * samples <= 0 and pt_renderer_render_until fail with a message naming the calls below;
+ * with samples > 0 they compute what they always did from S, Q and that number. */
+int pt_renderer_sample_counts(pt_renderer *r, int *tile_counts_host);
+/* pt_renderer_noise with nf = (float)count[tile] for the pixels of each tile: the same
+ * per-pixel expression in the same float32 order, the same fixed-order double sums, no
+ * atomics (a call repeats bit for bit).  A tile with fewer than 2 samples has tile_err
+ * +inf (*max_tile_err is then +inf) and adds nothing to *mean_err's sum, which is still
+ * divided by W*H. */
+int pt_renderer_adaptive_noise(pt_renderer *r, double *mean_err, float *max_tile_err,
+                               float *tile_err_host);
+/* The mean image S / (float)count[tile], 0 where the count is 0, W*H*3 floats into
+ * device_rgb_out (device memory, may be NULL) and/or host_rgb (may be NULL).  16-byte
+ * aligned buffers take the wide-access kernel.  Runs on the renderer's stream and
+ * synchronizes. */
+int pt_renderer_adaptive_mean(pt_renderer *r, void *device_rgb_out, float *host_rgb);
+/* The BMP of that mean M with pt_renderer_render_image's conversion: bytes
+ * (int)(M * 255.0f) & 0xFF, rows bottom-up. */
+int pt_renderer_render_image_adaptive(pt_renderer *r, const char *bmp_path);
+/* Renders masked chunks of check_every iterations (<= 0: 32; the last chunk is cut at
+ * max_iters), every tile active at first.  After each chunk that brings this call's count
+ * to max(min_iters, 2) or more it evaluates pt_renderer_adaptive_noise over every sample in
+ * the accumulator and switches off each active tile with tile_err <= tile_target; a tile
+ * switched off stays off for the rest of the call.  Returns 1 when no tile is active, 0 when
+ * max_iters is reached first, < 0 on error.  *iters_done = iterations this call rendered,
+ * *pixel_samples = sum over chunks of (pixels of the active tiles, dropped ones included)
+ * x chunk length, *mean_err = the last estimate's frame mean.  Each check synchronizes and
+ * reads the tile map back, as pt_renderer_render_until does.
+ * Known bias: a tile is stopped on an estimate made from the very samples it keeps, so
+ * tiles that look quiet by chance stop early and stay that way; min_iters is the guard.
+ * Like the "Limit" of pt_renderer_noise, this is a budget heuristic, not a statistic. */
+int pt_renderer_render_adaptive(pt_renderer *r, int first_iter, int min_iters, int max_iters,
+                                int check_every, double tile_target,
+                                int *iters_done, long long *pixel_samples, double *mean_err);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

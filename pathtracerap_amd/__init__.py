@@ -127,6 +127,15 @@ EXPORTS = [
     ("pt_renderer_render_image_denoised", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int,
                                                          ctypes.POINTER(_DenoiseParams)]),
     ("pt_renderer_denoise_times", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+    ("pt_renderer_render_loop_masked", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_ubyte)]),
+    ("pt_renderer_sample_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
+    ("pt_renderer_adaptive_noise", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _P_F, _P_F]),
+    ("pt_renderer_adaptive_mean", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _P_F]),
+    ("pt_renderer_render_image_adaptive", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    ("pt_renderer_render_adaptive", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_double, _P_I, ctypes.POINTER(ctypes.c_longlong),
+                                                   ctypes.POINTER(ctypes.c_double)]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -519,6 +528,63 @@ class Renderer:
         ms = (ctypes.c_double * 9)()
         _err(lib().pt_renderer_denoise_times(self._h, ms, 9), "denoise_times")
         return dict(prep=ms[0], passes=[ms[1 + i] for i in range(DENOISE_MAX_PASSES)], out=ms[7], total=ms[8])
+
+    def _tiles(self):
+        return (self.cfg.height + NOISE_TILE - 1) // NOISE_TILE, (self.cfg.width + NOISE_TILE - 1) // NOISE_TILE
+
+    def render_masked(self, mask=None, first_iter: int = 0, n_iters: int | None = None, sync: bool = True) -> None:
+        """Iterations that sample only the 16 x 16 tiles whose ``mask`` entry is non-zero
+        ((ceil(H/16), ceil(W/16)), any integer or bool dtype; None: every tile); needs
+        enable_moments (include/pathtracer_amd.h, pt_renderer_render_loop_masked).  The
+        mask is copied before the call returns."""
+        n = self.cfg.iterations if n_iters is None else n_iters
+        ptr = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.shape != self._tiles():
+                raise PathTracerError(f"render_masked: mask shape {m.shape}, tiles {self._tiles()}")
+            ptr = m.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))
+        _err(lib().pt_renderer_render_loop_masked(self._h, int(first_iter), int(n), ptr), "render_masked")
+        if sync:
+            self.synchronize()
+
+    def sample_counts(self) -> np.ndarray:
+        """Samples per tile since allocateOnGPU / clearImage, (ceil(H/16), ceil(W/16)) int32."""
+        out = np.zeros(self._tiles(), np.int32)
+        _err(lib().pt_renderer_sample_counts(self._h, _ip(out)), "sample_counts")
+        return out
+
+    def adaptive_noise(self) -> dict:
+        """noise() with each tile's own sample count (pt_renderer_adaptive_noise): ``mean``,
+        ``max_tile`` and the ``tiles`` map; a tile with fewer than 2 samples reads inf."""
+        tiles = np.zeros(self._tiles(), np.float32)
+        mean, mx = ctypes.c_double(), ctypes.c_float()
+        _err(lib().pt_renderer_adaptive_noise(self._h, ctypes.byref(mean), ctypes.byref(mx), _fp(tiles)), "adaptive_noise")
+        return dict(mean=mean.value, max_tile=np.float32(mx.value), tiles=tiles)
+
+    def adaptive_mean(self, out_ptr: int | None = None, keepalive=None) -> np.ndarray:
+        """The mean image S / count[tile] (0 where a tile has no sample), (W*H, 3) float32.
+        ``out_ptr``: a caller-owned W*H*3 float device buffer that receives it too."""
+        self._adaptive_ref = keepalive
+        img = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
+        _err(lib().pt_renderer_adaptive_mean(self._h, ctypes.c_void_p(int(out_ptr)) if out_ptr else None, _fp(img)),
+             "adaptive_mean")
+        return img
+
+    def renderImageAdaptive(self, path: str = "Render.bmp") -> None:
+        """The BMP of adaptive_mean() (renderImage's conversion of M * 255)."""
+        _err(lib().pt_renderer_render_image_adaptive(self._h, os.fsencode(path)), "renderImageAdaptive")
+
+    def render_adaptive(self, tile_target: float, max_iters: int, min_iters: int = 2, check_every: int = 32,
+                        first_iter: int = 0):
+        """Render masked chunks of ``check_every`` iterations, switching off every tile whose
+        estimate is at most ``tile_target``, until none is active or ``max_iters`` are done
+        -> (converged, iters, pixel_samples, mean)."""
+        done, taken, mean = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_double()
+        rc = _err(lib().pt_renderer_render_adaptive(self._h, int(first_iter), int(min_iters), int(max_iters),
+                                                    int(check_every), float(tile_target), ctypes.byref(done),
+                                                    ctypes.byref(taken), ctypes.byref(mean)), "render_adaptive")
+        return bool(rc), done.value, taken.value, mean.value
 
     def free(self) -> None:
         if self._h:

@@ -352,6 +352,25 @@ int pt_renderer_denoise_times(pt_renderer* r, double* ms, int n) {
     if (!ms || n < 0) return set_err("bad arguments");
     R_CALL(r->r->denoiseTimes(ms, n));
 }
+int pt_renderer_render_loop_masked(pt_renderer* r, int first_iter, int n_iters, const unsigned char* tile_mask_host) {
+    R_CALL(r->r->renderLoopMasked(first_iter, n_iters, tile_mask_host));
+}
+int pt_renderer_sample_counts(pt_renderer* r, int* tile_counts_host) { R_CALL(r->r->sampleCounts(tile_counts_host)); }
+int pt_renderer_adaptive_noise(pt_renderer* r, double* mean_err, float* max_tile_err, float* tile_err_host) {
+    R_CALL(r->r->adaptiveNoise(mean_err, max_tile_err, tile_err_host));
+}
+int pt_renderer_adaptive_mean(pt_renderer* r, void* device_rgb_out, float* host_rgb) {
+    R_CALL(r->r->adaptiveMean((float*)device_rgb_out, host_rgb));
+}
+int pt_renderer_render_image_adaptive(pt_renderer* r, const char* path) {
+    if (!path) return set_err("bad arguments");
+    R_CALL(r->r->renderImageAdaptive(path));
+}
+int pt_renderer_render_adaptive(pt_renderer* r, int first_iter, int min_iters, int max_iters, int check_every,
+                                double tile_target, int* iters_done, long long* pixel_samples, double* mean_err) {
+    R_CALL(r->r->renderAdaptive(first_iter, min_iters, max_iters, check_every, tile_target, iters_done, pixel_samples,
+                                mean_err));
+}
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;

@@ -1,6 +1,7 @@
-// film.hip -- per-pixel second moment, noise estimate, render-until-converged and
-// the variance-guided edge-avoiding denoiser (no counterpart in the reference, which
-// renders a fixed ITER samples and writes the raw mean).
+// film.hip -- per-pixel second moment, noise estimate, render-until-converged, the
+// variance-guided edge-avoiding denoiser, and the host side of tile-masked sampling
+// with its per-tile estimate, mean and adaptive loop (no counterpart in the reference,
+// which renders a fixed ITER samples and writes the raw mean).
 //
 // Every pixel receives one contribution c = sqrt(color) per iteration.  With
 // moments on, every pipeline (a single one too) writes c to its contribution
@@ -132,6 +133,69 @@ __global__ __launch_bounds__(256) void k_noise_final(const double* __restrict__ 
     if (threadIdx.x == 0) {
         *out_mean = t / npix;
         *out_max = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    }
+}
+
+// k_noise_tiles with a sample count per tile (adaptive sampling): nf = (float)counts[tile],
+// the same pixel_err and the same fixed-order sum.  A tile with fewer than 2 samples has
+// no estimate: error +inf, and 0 in the sum the frame mean is made of.
+__global__ __launch_bounds__(kTileWG) void k_noise_tiles_counts(const float* __restrict__ S, const float* __restrict__ Q,
+                                                                int W, int H, int tiles_x, const int* __restrict__ counts,
+                                                                double* __restrict__ tile_sum, float* __restrict__ tile_err) {
+    __shared__ double s_part[kTileWG / 64];
+    const int cnt = counts[blockIdx.x];
+    if (cnt < 2) {                          // the whole workgroup leaves, before the barrier
+        if (threadIdx.x == 0) {
+            tile_sum[blockIdx.x] = 0.0;
+            tile_err[blockIdx.x] = INFINITY;
+        }
+        return;
+    }
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int x = tx * kTile + (threadIdx.x % kTile), y = ty * kTile + (threadIdx.x / kTile);
+    double err = 0.0;
+    if (x < W && y < H) err = (double)pixel_err(S, Q, (size_t)y * W + x, (float)cnt);
+    const double t = block_sum<kTileWG / 64>(err, s_part);
+    if (threadIdx.x == 0) {
+        const int rw = W - tx * kTile, rh = H - ty * kTile;
+        const int pw = rw < kTile ? rw : kTile, ph = rh < kTile ? rh : kTile;
+        tile_sum[blockIdx.x] = t;
+        tile_err[blockIdx.x] = (float)(t / (double)(pw * ph));
+    }
+}
+
+// Float i of the W*H*3 sums over its tile's sample count (0 where the tile has none).
+__device__ inline float mean_by_count(float s, size_t i, int W, int tiles_x, const int* __restrict__ counts) {
+    const size_t px = i / 3;
+    const int y = (int)(px / (size_t)W), x = (int)(px - (size_t)y * W);
+    const int c = counts[(y / kTile) * tiles_x + (x / kTile)];
+    return c > 0 ? s / (float)c : 0.0f;
+}
+
+// out = S / (float)counts[tile], n = W*H*3 floats.  Memory bound (one stream read, one
+// written): VEC moves 16 bytes per lane and needs 16-byte aligned S and out; buffers
+// with less alignment take the scalar variant, as in k_merge_m2.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_mean_counts(const float* __restrict__ S, float* __restrict__ out, size_t n, int W,
+                                                     int tiles_x, const int* __restrict__ counts) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const size_t n4 = n >> 2;
+        if (i < n4) {
+            const float4 s = reinterpret_cast<const float4*>(S)[i];
+            float4 m;
+            m.x = mean_by_count(s.x, 4 * i, W, tiles_x, counts);
+            m.y = mean_by_count(s.y, 4 * i + 1, W, tiles_x, counts);
+            m.z = mean_by_count(s.z, 4 * i + 2, W, tiles_x, counts);
+            m.w = mean_by_count(s.w, 4 * i + 3, W, tiles_x, counts);
+            reinterpret_cast<float4*>(out)[i] = m;
+        }
+        if (i < (n & 3)) {                  // the last n % 4 floats
+            const size_t j = (n4 << 2) + i;
+            out[j] = mean_by_count(S[j], j, W, tiles_x, counts);
+        }
+    } else if (i < n) {
+        out[i] = mean_by_count(S[i], i, W, tiles_x, counts);
     }
 }
 
@@ -395,6 +459,7 @@ int Renderer::readMoments(float* host_m2) {
 int Renderer::noise(int samples, double* mean_err, float* max_tile_err, float* tile_err_host) {
     if (!allocated) { last_error = "not allocated"; return -1; }
     if (!moments_on) { last_error = "moments not enabled"; return -1; }
+    if (samples <= 0 && !countsUniform()) return refuseMixedCounts("noise");
     if (samples <= 0) samples = samples_accumulated;
     if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
     const int tx = noiseTilesX(), ty = noiseTilesY(), nt = tx * ty;
@@ -425,6 +490,7 @@ int Renderer::renderUntil(int first_iter, int min_iters, int max_iters, int chec
     if (!allocated) { last_error = "not allocated"; return -1; }
     if (!moments_on) { last_error = "moments not enabled"; return -1; }
     if (first_iter < 0 || max_iters < 1) { last_error = "bad iteration range"; return -1; }
+    if (!countsUniform()) return refuseMixedCounts("render_until");      // it stops on noise(0)
     if (check_every <= 0) check_every = 32;
     const int min_check = std::max(min_iters, 2);
     int done = 0, converged = 0;
@@ -483,6 +549,7 @@ int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, flo
                       float* host_var) {
     if (!allocated) { last_error = "not allocated"; return -1; }
     if (!moments_on) { last_error = "moments not enabled"; return -1; }
+    if (samples <= 0 && !countsUniform()) return refuseMixedCounts("denoise");
     if (samples <= 0) samples = samples_accumulated;
     if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
     if (passes < 1 || passes > PT_DENOISE_MAX_PASSES || !std::isfinite(sigma_l) || !(sigma_l > 0.0f) ||
@@ -595,6 +662,200 @@ int Renderer::renderImageDenoised(const std::string& path, int samples, int pass
     std::vector<float> img((size_t)cfg.width * cfg.height * 3);
     if (denoise(samples, passes, sigma_l, sigma_z, nullptr, img.data(), nullptr) != 0) return -1;
     return writeBmp(path, img.data(), 1.0f);         // x * 1.0f is x
+}
+
+// ---------------------------------------------------------------------------
+// Tile-masked sampling and the adaptive render.  The mask and the counts use the noise
+// estimate's tiles.  Nothing here is allocated until the first masked or adaptive call.
+// ---------------------------------------------------------------------------
+bool Renderer::countsUniform() const {
+    for (int c : tile_counts)
+        if (c != tile_counts[0]) return false;
+    return true;
+}
+
+int Renderer::refuseMixedCounts(const char* call) {
+    last_error = std::string(call) + ": tiles have different sample counts after masked iterations; pass samples > 0, or use "
+                 "pt_renderer_adaptive_noise / pt_renderer_adaptive_mean / pt_renderer_render_adaptive";
+    return -1;
+}
+
+// Device mask and counts, and the pinned staging ring of the mask uploads: a slot is
+// written again only after the copy that read it has completed (its event).
+int Renderer::allocAdaptive() {
+    if (tile_mask_dev) return 0;
+    const size_t nt = (size_t)noiseTilesX() * noiseTilesY();
+    void* d = nullptr;
+    PT_HIP(hipMalloc(&d, nt * sizeof(int)));
+    allocs.push_back(d);
+    tile_counts_dev = (int*)d;
+    PT_HIP(hipHostMalloc(&d, nt * kMaskSlots, hipHostMallocDefault));
+    mask_stage = (unsigned char*)d;
+    for (int i = 0; i < kMaskSlots; i++) PT_HIP(hipEventCreateWithFlags(&mask_ev[i], hipEventDisableTiming));
+    mask_slot = 0;
+    PT_HIP(hipMalloc(&d, nt));
+    allocs.push_back(d);
+    tile_mask_dev = (unsigned char*)d;
+    return 0;
+}
+
+// freeBuffers: the streams are idle; the device buffers go with `allocs`
+void Renderer::freeAdaptive() {
+    if (mask_stage) hipHostFree(mask_stage);
+    mask_stage = nullptr;
+    for (int i = 0; i < kMaskSlots; i++) {
+        if (mask_ev[i]) hipEventDestroy(mask_ev[i]);
+        mask_ev[i] = nullptr;
+    }
+    tile_mask_dev = nullptr;
+    tile_counts_dev = nullptr;
+    am_out = nullptr;
+}
+
+int Renderer::uploadTileCounts() {
+    if (allocAdaptive() != 0) return -1;
+    // the callers synchronize before they return, and the counts change only in host calls
+    PT_HIP(hipMemcpyAsync(tile_counts_dev, tile_counts.data(), tile_counts.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+int Renderer::renderLoopMasked(int first_iter, int n_iters, const unsigned char* tile_mask_host) {
+    if (!allocated) { last_error = "render_loop_masked before allocateOnGPU"; return -1; }
+    if (!moments_on) { last_error = "moments not enabled (masked iterations need pt_renderer_enable_moments)"; return -1; }
+    if (n_iters < 0 || first_iter < 0) { last_error = "bad iteration range"; return -1; }
+    const size_t nt = tile_counts.size();
+    size_t active = nt;
+    if (tile_mask_host) {
+        active = 0;
+        for (size_t t = 0; t < nt; t++) active += tile_mask_host[t] != 0;
+    }
+    if (active == 0 || n_iters == 0) return 0;       // nothing to sample: nothing enqueued, nothing changed
+    if (allocAdaptive() != 0) return -1;
+    // The mask goes up on the caller's stream, before renderIters forks the pipeline
+    // streams off it and after the join of every earlier call: the iterations of an
+    // earlier masked call have read their mask before this copy overwrites it.
+    unsigned char* stage = mask_stage + (size_t)mask_slot * nt;
+    PT_HIP(hipEventSynchronize(mask_ev[mask_slot]));         // the copy that last read this slot (none: returns at once)
+    for (size_t t = 0; t < nt; t++) stage[t] = tile_mask_host ? (tile_mask_host[t] != 0) : 1;
+    PT_HIP(hipMemcpyAsync(tile_mask_dev, stage, nt, hipMemcpyHostToDevice, stream));
+    PT_HIP(hipEventRecord(mask_ev[mask_slot], stream));
+    mask_slot = (mask_slot + 1) % kMaskSlots;
+    int done = 0;
+    const int rc = renderIters(first_iter, n_iters, tile_mask_dev, &done);
+    for (size_t t = 0; t < nt; t++)
+        if (stage[t]) tile_counts[t] += done;
+    return rc;
+}
+
+int Renderer::sampleCounts(int* tile_counts_host) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (tile_counts_host) std::copy(tile_counts.begin(), tile_counts.end(), tile_counts_host);
+    return (int)tile_counts.size();
+}
+
+int Renderer::adaptiveNoise(double* mean_err, float* max_tile_err, float* tile_err_host) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!moments_on) { last_error = "moments not enabled"; return -1; }
+    if (uploadTileCounts() != 0) return -1;
+    const int tx = noiseTilesX(), ty = noiseTilesY(), nt = tx * ty;
+    hipLaunchKernelGGL(k_noise_tiles_counts, dim3((unsigned)nt), dim3(kTileWG), 0, stream, kp.image, m2, cfg.width,
+                       cfg.height, tx, tile_counts_dev, noise_sum, noise_err);
+    PT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, stream, noise_sum, noise_err, nt,
+                       (double)cfg.width * (double)cfg.height, noise_sum + nt, noise_err + nt);
+    PT_HIP(hipGetLastError());
+    double mean = 0.0;
+    float mx = 0.0f;
+    PT_HIP(hipMemcpyAsync(&mean, noise_sum + nt, sizeof mean, hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipMemcpyAsync(&mx, noise_err + nt, sizeof mx, hipMemcpyDeviceToHost, stream));
+    if (tile_err_host)
+        PT_HIP(hipMemcpyAsync(tile_err_host, noise_err, (size_t)nt * sizeof(float), hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    if (checkFaults() != 0) return -1;
+    if (mean_err) *mean_err = mean;
+    if (max_tile_err) *max_tile_err = mx;
+    return 0;
+}
+
+int Renderer::adaptiveMean(float* device_rgb_out, float* host_rgb) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (uploadTileCounts() != 0) return -1;
+    const size_t n3 = (size_t)cfg.width * cfg.height * 3;
+    float* out = device_rgb_out;
+    if (!out) {
+        if (!am_out) {
+            void* d = nullptr;
+            PT_HIP(hipMalloc(&d, n3 * sizeof(float)));
+            allocs.push_back(d);
+            am_out = (float*)d;
+        }
+        out = am_out;
+    }
+    const bool vec = (((uintptr_t)kp.image | (uintptr_t)out) & 15) == 0;
+    if (vec) {
+        const size_t n4 = n3 >> 2;
+        hipLaunchKernelGGL(k_mean_counts<true>, dim3((unsigned)std::max<size_t>(1, (n4 + 255) / 256)), dim3(256), 0, stream,
+                           kp.image, out, n3, cfg.width, noiseTilesX(), tile_counts_dev);
+    } else {
+        hipLaunchKernelGGL(k_mean_counts<false>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream,
+                           kp.image, out, n3, cfg.width, noiseTilesX(), tile_counts_dev);
+    }
+    PT_HIP(hipGetLastError());
+    if (host_rgb) PT_HIP(hipMemcpyAsync(host_rgb, out, n3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    return checkFaults();
+}
+
+int Renderer::renderImageAdaptive(const std::string& path) {
+    std::vector<float> img((size_t)cfg.width * cfg.height * 3);
+    if (adaptiveMean(nullptr, img.data()) != 0) return -1;
+    return writeBmp(path, img.data(), 1.0f);         // x * 1.0f is x
+}
+
+// Chunks of check_every masked iterations, every tile active at first; after each chunk
+// that brings this call's count to max(min_iters, 2) or more, the per-tile estimate over
+// every sample in the accumulator switches off, for the rest of the call, the tiles at or
+// below tile_target.  1: no tile is active any more, 0: max_iters reached.
+int Renderer::renderAdaptive(int first_iter, int min_iters, int max_iters, int check_every, double tile_target,
+                             int* iters_done, long long* pixel_samples, double* mean_err) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!moments_on) { last_error = "moments not enabled"; return -1; }
+    if (first_iter < 0 || max_iters < 1) { last_error = "bad iteration range"; return -1; }
+    if (check_every <= 0) check_every = 32;
+    const int min_check = std::max(min_iters, 2);
+    const int tx = noiseTilesX(), ty = noiseTilesY(), nt = tx * ty;
+    std::vector<unsigned char> mask((size_t)nt, 1);
+    std::vector<float> terr((size_t)nt);
+    auto tile_pixels = [&](int t) {
+        const int rw = cfg.width - (t % tx) * kTile, rh = cfg.height - (t / tx) * kTile;
+        return (long long)std::min(rw, kTile) * std::min(rh, kTile);
+    };
+    int done = 0, n_active = nt;
+    long long taken = 0, active_pixels = (long long)cfg.width * cfg.height;
+    double mean = -1.0;
+    bool fresh = false;
+    while (done < max_iters && n_active > 0) {
+        const int n = std::min(check_every, max_iters - done);
+        if (renderLoopMasked(first_iter + done, n, mask.data()) != 0) return -1;
+        done += n;
+        taken += active_pixels * n;
+        fresh = false;
+        if (done >= min_check) {
+            if (adaptiveNoise(&mean, nullptr, terr.data()) != 0) return -1;
+            fresh = true;
+            n_active = 0;
+            active_pixels = 0;
+            for (int t = 0; t < nt; t++) {
+                if (mask[t] && (double)terr[t] <= tile_target) mask[t] = 0;
+                if (mask[t]) { n_active++; active_pixels += tile_pixels(t); }
+            }
+        }
+    }
+    if (!fresh && adaptiveNoise(&mean, nullptr, nullptr) != 0) return -1;     // min_iters beyond max_iters
+    if (iters_done) *iters_done = done;
+    if (pixel_samples) *pixel_samples = taken;
+    if (mean_err) *mean_err = mean;
+    return n_active == 0 ? 1 : 0;
 }
 
 }  // namespace pt

@@ -3,10 +3,16 @@
 //
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
+//                  [--adaptive X [--check-every N] [--min-iter N]]
 //
 // --noise-target X: render until the mean relative noise estimate (pt_renderer_noise)
 // is at most X, checked every N iterations (default 32); --iter is then the most
 // iterations to render, and the BMP is divided by the iterations actually rendered.
+//
+// --adaptive X: tile-based adaptive sampling (pt_renderer_render_adaptive): a 16 x 16 tile
+// stops receiving samples once its noise estimate is at most X, checked every N iterations
+// (default 32) from --min-iter (default 2) on; --iter is the most iterations, and the BMP
+// is the per-tile mean (pt_renderer_render_image_adaptive).
 //
 // --denoise: keep the second moments and write the BMP of the denoised mean
 // (pt_renderer_render_image_denoised over the iterations actually rendered, N a-trous
@@ -28,7 +34,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
-                             "[--denoise [--denoise-passes N]]\n", argv[0]);
+                             "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -39,6 +45,8 @@ int main(int argc, char** argv) {
     const char* out = "Render.bmp";
     double noise_target = -1.0;          // < 0: render cfg.iterations
     int check_every = 32;
+    double adaptive_target = -1.0;       // >= 0: tile-based adaptive sampling
+    int min_iter = 2;
     bool denoise = false;
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
@@ -52,19 +60,35 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pipelines") && i + 1 < argc) cfg.pipelines = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--noise-target") && i + 1 < argc) noise_target = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--check-every") && i + 1 < argc) check_every = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) adaptive_target = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--min-iter") && i + 1 < argc) min_iter = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
     }
+    if (adaptive_target >= 0 && (noise_target >= 0 || denoise)) {
+        std::fprintf(stderr, "--adaptive excludes --noise-target and --denoise\n");
+        return 2;
+    }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
-    if (!r || ((noise_target >= 0 || denoise) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
+    if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }
     int iters = cfg.iterations;
     auto t0 = std::chrono::high_resolution_clock::now();
-    if (noise_target >= 0) {
+    if (adaptive_target >= 0) {
+        double mean = 0.0;
+        long long taken = 0;
+        const int rc = pt_renderer_render_adaptive(r, 0, min_iter, cfg.iterations, check_every, adaptive_target, &iters,
+                                                   &taken, &mean);
+        if (rc < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+        const double full = (double)iters * cfg.width * cfg.height;
+        std::printf("%s after %d of at most %d iterations: %lld pixel samples, %.1f %% of iterations x pixels; "
+                    "noise estimate %.6g (tile target %.6g)\n", rc ? "Every tile converged" : "Not every tile converged",
+                    iters, cfg.iterations, taken, full > 0 ? 100.0 * (double)taken / full : 0.0, mean, adaptive_target);
+    } else if (noise_target >= 0) {
         double mean = 0.0;
         const int rc = pt_renderer_render_until(r, 0, 2, cfg.iterations, check_every, noise_target, &iters, &mean);
         if (rc < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
@@ -78,7 +102,8 @@ int main(int argc, char** argv) {
     double us = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
     long long seg = pt_renderer_segments(r);
     std::printf("Full run: %.0f microseconds, %lld ray segments, %.2f Mrays/s\n", us, seg, seg / us);
-    if ((denoise ? pt_renderer_render_image_denoised(r, out, iters, &dn) : pt_renderer_render_image(r, out, iters)) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+    if ((adaptive_target >= 0 ? pt_renderer_render_image_adaptive(r, out)
+         : denoise ? pt_renderer_render_image_denoised(r, out, iters, &dn) : pt_renderer_render_image(r, out, iters)) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer_free(r);
     pt_scene_destroy(s);
     return 0;

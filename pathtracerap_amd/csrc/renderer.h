@@ -170,6 +170,16 @@ public:
                 float* host_var);
     int renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z);
     int denoiseTimes(double* ms, int n);             // HIP-event times of the last denoise call under setProfiling
+    // Tile-masked sampling and the adaptive render (no counterpart in the reference): iterations whose
+    // first bounce emits only the rays of the active 16 x 16 tiles, per-tile sample counts, the estimate
+    // and the mean that divide by them, and the loop that switches converged tiles off
+    int renderLoopMasked(int first_iter, int n_iters, const unsigned char* tile_mask_host);
+    int sampleCounts(int* tile_counts_host);         // returns the tile count
+    int adaptiveNoise(double* mean_err, float* max_tile_err, float* tile_err_host);
+    int adaptiveMean(float* device_rgb_out, float* host_rgb);
+    int renderImageAdaptive(const std::string& path);
+    int renderAdaptive(int first_iter, int min_iters, int max_iters, int check_every, double tile_target,
+                       int* iters_done, long long* pixel_samples, double* mean_err);
 
     RenderConfig cfg;
     std::string last_error;
@@ -182,7 +192,14 @@ private:
     int allocPipe(KParams& k, size_t cap, hipStream_t st);
     int fail(hipError_t e, const char* what);
     void freeBuffers();
-    int enqueueIteration(int q, hipStream_t st, int iter, int passes);
+    int enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask = nullptr);
+    int renderIters(int first_iter, int n_iters, const unsigned char* tile_mask, int* done_out);
+    void launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, int iter, const unsigned char* tile_mask);
+    int allocAdaptive();
+    void freeAdaptive();
+    int uploadTileCounts();
+    bool countsUniform() const;
+    int refuseMixedCounts(const char* call);
     void dropGraphs();
     int joinPipes(int np);
     int checkFaults();
@@ -219,6 +236,14 @@ private:
     float* dn_slope = nullptr;       // depth slope
     std::vector<hipEvent_t> dn_events;   // profiling: around prep, each pass and the output copy
     int dn_event_passes = 0;
+    std::vector<int> tile_counts;        // samples per noise tile since allocateOnGPU / clearImage (host)
+    static constexpr int kMaskSlots = 4;     // masked calls whose mask copy may be in flight at once
+    unsigned char* tile_mask_dev = nullptr;  // the mask the enqueued masked iterations read; set by the first masked call
+    unsigned char* mask_stage = nullptr;     // pinned host staging, kMaskSlots masks
+    hipEvent_t mask_ev[kMaskSlots]{};        // slot i's upload has completed
+    int mask_slot = 0;
+    int* tile_counts_dev = nullptr;      // adaptiveNoise / adaptiveMean: the counts, uploaded per call
+    float* am_out = nullptr;             // adaptiveMean's result when the caller gives no device buffer
     int profiling = 0;
     std::vector<void*> allocs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> bounce_events, first_events, scan_events, trace_events, sort_events;

@@ -2642,6 +2642,74 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
 
+// k_bounce<true, *, BS> under a tile mask (tile-masked sampling; moments are on, so the
+// contributions go through p.contrib).  A pixel of an active 16 x 16 tile does what
+// k_bounce does: camera ray, cached primary hit, shade with slot = pixel index, stable
+// compaction.  A pixel of an inactive tile emits no ray, reads no cache entry and writes
+// contribution 0.0, which the merge adds to S and Q without changing a bit.  A 64-lane
+// wave covers 64 consecutive pixel indices: up to four tiles of a row, more across a row
+// end, so the mask is read per lane.  A block with no active tile still writes
+// blk_cnt[chunk] = 0, which the untouched k_scan reads.
+template <int BS>
+__global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, int iter,
+                                                                    const unsigned char* __restrict__ tile_mask, int tiles_x) {
+    __shared__ int s_wave[BS / 64];
+    const int n = p.npix;
+    const int chunk = blockIdx.x;
+    const int j0 = chunk >= (n + BS - 1) / BS ? n : chunk * BS;
+    if (j0 >= n) return;                       // whole block idle (uniform)
+    const int j = j0 + threadIdx.x;
+    const bool inside = j < n;
+    bool active = false;
+    if (inside) {
+        const int y = j / p.width, x = j - y * p.width;
+        active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
+    }
+    RayState r;
+    if (active) {
+        Hit h;
+        camera_ray(p, j, r.o, r.d);
+        r.c = mk3(1.0f, 1.0f, 1.0f);
+        r.pixel = j;
+        r.bounces = p.max_bounces;
+        const float4 ch = p.cache_hit[j];
+        h.dist = ch.x;
+        h.n = mk3(ch.y, ch.z, ch.w);
+        h.model = p.cache_model[j];
+        shade(p, r, h, iter, j);
+    }
+    const bool alive = active && r.bounces > 0;
+    if (inside && !alive) {
+        float* cp = p.contrib + 3 * (size_t)j;
+        cp[0] = active ? 1.0f * sqrtf(r.c.x) : 0.0f;
+        cp[1] = active ? 1.0f * sqrtf(r.c.y) : 0.0f;
+        cp[2] = active ? 1.0f * sqrtf(r.c.z) : 0.0f;
+    }
+    const unsigned long long m = __ballot(alive);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    int base = 0, total = 0;
+    if (BS > 64) {
+        if (lane == 0) s_wave[wid] = __popcll(m);
+        __syncthreads();
+    } else {
+        total = __popcll(m);
+    }
+#pragma unroll
+    for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
+        const int c = s_wave[w];
+        base += (w < wid) ? c : 0;
+        total += c;
+    }
+    if (alive) {
+        const int dst = j0 + base + rank;
+        p.ray[0][0][dst] = make_float4(r.o.x, r.o.y, r.o.z, __int_as_float(r.pixel));
+        p.ray[0][1][dst] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(r.bounces));
+        p.ray[0][2][dst] = make_float4(r.c.x, r.c.y, r.c.z, 0.0f);
+    }
+    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+}
+
 // One workgroup: exclusive scan of survivor counts of bounce `bounce`,
 // live count for bounce+1, and the first source block of every
 // destination block (dst_start).  A small workgroup with almost no LDS: it
@@ -3251,6 +3319,7 @@ int Renderer::clearImage() {
         PT_HIP(hipGetLastError());
     }
     samples_accumulated = 0;
+    tile_counts.assign((size_t)noiseTilesX() * noiseTilesY(), 0);
     // a fault invalidated the image it was counted against; the cleared image starts
     // a new render, so later checks report only faults of renders after this point
     PT_HIP(hipMemsetAsync(kp.segments + kTraceFaultCounter, 0, sizeof(unsigned long long), stream));
@@ -3343,6 +3412,16 @@ void Renderer::launchBounce(const KParams& k, hipStream_t st, bool first, dim3 g
     }
 }
 
+// Bounce 0 of a masked iteration (renderLoopMasked): tile_mask is the device copy of the mask.
+void Renderer::launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, int iter, const unsigned char* tile_mask) {
+    const int tx = noiseTilesX();
+    switch (k.chunk) {
+        case 64: hipLaunchKernelGGL(k_bounce_masked<64>, grid, dim3(64), 0, st, k, iter, tile_mask, tx); break;
+        case 128: hipLaunchKernelGGL(k_bounce_masked<128>, grid, dim3(128), 0, st, k, iter, tile_mask, tx); break;
+        default: hipLaunchKernelGGL(k_bounce_masked<256>, grid, dim3(256), 0, st, k, iter, tile_mask, tx); break;
+    }
+}
+
 // Bounce b's ray sort (when the pipeline sorts) and persistent trace launches, as
 // every iteration enqueues them (and the trace_rays test hook).  pall / ptrace: an
 // event pair around the sort kernels / around the trace launches only.
@@ -3369,7 +3448,9 @@ int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pal
 
 // One iteration's bounce loop on pipeline q (stream st): sort / trace / shade /
 // scan per bounce.  iter = -1: k_bounce reads the id from k.iter_dev (capture).
-int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes) {
+// tile_mask (device, never under capture): bounce 0 is k_bounce_masked; from bounce 1
+// on every kernel sizes its work from n_live, so nothing else differs.
+int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask) {
     const KParams& k = pk[q];
     const dim3 grid((unsigned)kp.nblocks + 8u);
     // profiling 1: an event pair around every kernel group on every pipeline; 2: around the
@@ -3383,7 +3464,8 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes) {
             launchBounce(k, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-            launchBounce(k, st, b == 0, grid, iter, b, cfg.accel);
+            if (b == 0 && tile_mask) launchBounceMasked(k, st, grid, iter, tile_mask);
+            else launchBounce(k, st, b == 0, grid, iter, b, cfg.accel);
         }
         PT_HIP(hipGetLastError());
         if (pall) {
@@ -3409,7 +3491,19 @@ void Renderer::dropGraphs() {
 int Renderer::renderLoop(int first_iter, int n_iters) {
     if (!allocated) { last_error = "renderLoop before allocateOnGPU"; return -1; }
     if (n_iters < 0 || first_iter < 0) { last_error = "bad iteration range"; return -1; }
-    if (kp.npix == 0) { samples_accumulated += n_iters; return 0; }
+    int done = 0;
+    const int rc = renderIters(first_iter, n_iters, nullptr, &done);
+    for (int& c : tile_counts) c += done;            // every tile: host only
+    return rc;
+}
+
+// renderLoop's iterations (tile_mask null) or renderLoopMasked's (the device mask, uploaded
+// on the caller's stream before this call): masked iterations are enqueued directly,
+// never captured and never replayed, so the graphs of the plain loop stay as they are.
+// *done = iterations enqueued.
+int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile_mask, int* done_out) {
+    *done_out = 0;
+    if (kp.npix == 0) { samples_accumulated += n_iters; *done_out = n_iters; return 0; }
     if (!kp.image || !kp.cache_hit || !kp.models) { last_error = "renderLoop: device buffers missing"; return -1; }
     if (!cache_valid) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -3439,7 +3533,7 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
         const int q = it % np;
         const KParams& k = pk[q];
         hipStream_t st = q == 0 ? stream : pstream[q];
-        if (use_graph && !profiling && st) {   // (no capture on the legacy null stream)
+        if (use_graph && !profiling && st && !tile_mask) {   // (no capture on the legacy null stream)
             // The bounce loop's launches are identical every iteration but for the
             // iteration id: capture them once per pipeline (k_bounce reads the id from
             // k.iter_dev) and replay the graph after one k_set_iter.
@@ -3457,7 +3551,7 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
                 PT_HIP(ei);
             }
             PT_HIP(hipGraphLaunch(gexec[q], st));
-        } else if (enqueueIteration(q, st, iter, passes) != 0) {
+        } else if (enqueueIteration(q, st, iter, passes, tile_mask) != 0) {
             return -1;
         }
         if (np > 1) {
@@ -3483,6 +3577,7 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
         if ((rc = body(done)) != 0) break;
     }
     samples_accumulated += done;
+    *done_out = done;
     const std::string err = last_error;
     const int jrc = joinPipes(np);
     if (rc != 0) { last_error = err; return -1; }     // the first failure is the one reported
@@ -3826,6 +3921,7 @@ void Renderer::freeBuffers() {
     dn_cv[0] = dn_cv[1] = dn_nd = nullptr;
     dn_model = nullptr;
     dn_slope = nullptr;
+    freeAdaptive();
     allocated = false;
     cache_valid = false;
 }
