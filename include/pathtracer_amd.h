@@ -364,6 +364,51 @@ int pt_renderer_render_image_adaptive(pt_renderer *r, const char *bmp_path);
 int pt_renderer_render_adaptive(pt_renderer *r, int first_iter, int min_iters, int max_iters,
                                 int check_every, double tile_target,
                                 int *iters_done, long long *pixel_samples, double *mean_err);
+
+/* ---- Pixel-jittered camera rays (anti-aliasing; added within ABI 9: new functions only,
+ * pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in the reference, whose
+ * camera rays are the same every iteration, so its silhouettes are stair-stepped at any
+ * sample count).  Off by default: a renderer that never turns it on allocates, launches and
+ * computes exactly what it did. ---- */
+/* Host state: it applies to the iterations enqueued after the call, and may be set before or
+ * after allocate_on_gpu and between render calls without a synchronize.  While on,
+ * pt_renderer_render_loop, _render_loop_masked, _render_until and _render_adaptive all enqueue
+ * jittered iterations.  width is the side of the square, in pixels, the ray's point is drawn
+ * from, centred on the point the unjittered ray goes through (1.0: the pixel's own extent).
+ * One jittered iteration `it`, for launched pixel p = y*W + x (pixels dropped by tail_drop
+ * stay dropped), float32 IEEE in exactly this order, no fused multiply-add:
+ *   ux = the first uniform of the reference's engine seeded (it, p, max_bounces + 1)
+ *   uy = the first uniform of the engine seeded (it, p, max_bounces + 2)
+ *        (depths the shading never seeds with; the index is the pixel, not the pool slot)
+ *   fx = (float)x + width * (ux - 0.5f);   fy = (float)y + width * (uy - 0.5f)
+ *   wx = (float)(plane_x0 + (double)(fx * step_x));  wy = (float)(plane_y0 + (double)(fy * step_y))
+ *   origin = cam;  direction = (wx, wy, plane_z) - cam (not normalised);  color = 1;
+ *   bounces = max_bounces
+ * The rays, in ascending pixel order, are bounce 0's survivors: the ray of rank k sits at
+ * dense slot k.  Nothing is intersected or shaded at bounce 0.  Then come the ordinary passes
+ * b = 1 .. max(max_bounces, 1): ray sort (when on), trace, shade, compaction -- so a ray gets
+ * as many shades as in pt_renderer_render_loop, and each pixel still contributes exactly once
+ * per iteration.  The RNG slot of a ray's first shade is its rank, which with every tile
+ * active is its pixel index, as in render_loop.  The generated rays are in pixel order
+ * already, so the trace of pass 1 claims them unsorted; PT_JITTER_SORT=1 (environment, read
+ * by allocate_on_gpu) sorts them like every later pass's.  The results are the same.
+ * Width 0: x + 0 * (u - 0.5f) is x, so on with width 0 reproduces render_loop bit for bit.
+ * Masks: under a tile mask (moments required, as ever) a pixel of an inactive tile emits no
+ * ray and contributes 0.0.  Sharding: the offset depends on (iteration, pixel) only, so
+ * sharding the iterations across ranks stays exact.
+ * Unchanged: the primary-hit cache is still built once; pt_renderer_primary_hits, the
+ * denoiser's guides and unjittered iterations read it.  Limit: the denoiser's guides are thus
+ * the hit of the unjittered ray, so an anti-aliased edge pixel, a mix of two surfaces, is
+ * filtered with the guides of one of them.  pt_renderer_segments counts a jittered iteration's
+ * generated rays as bounce 0 (the frame's launched pixels, as for masked iterations) and its
+ * traced camera rays as bounce 1: the launched-pixel count more per iteration than
+ * render_loop.  Jittered iterations are enqueued directly also under PT_GRAPH=1: never
+ * captured or replayed, and the graphs of the unjittered loop stay valid.
+ * Refused before any launch: a null renderer; a width that is not finite or is negative;
+ * turning it on when max_bounces + 2 > 511 (the seeding word's depth field). */
+int pt_renderer_set_pixel_jitter(pt_renderer *r, int on, float width);
+/* The current setting (either pointer may be NULL); off and width 1.0 until set. */
+int pt_renderer_pixel_jitter(pt_renderer *r, int *on, float *width);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

@@ -136,6 +136,8 @@ EXPORTS = [
     ("pt_renderer_render_adaptive", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_double, _P_I, ctypes.POINTER(ctypes.c_longlong),
                                                    ctypes.POINTER(ctypes.c_double)]),
+    ("pt_renderer_set_pixel_jitter", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
+    ("pt_renderer_pixel_jitter", ctypes.c_int, [ctypes.c_void_p, _P_I, _P_F]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -585,6 +587,20 @@ class Renderer:
                                                     int(check_every), float(tile_target), ctypes.byref(done),
                                                     ctypes.byref(taken), ctypes.byref(mean)), "render_adaptive")
         return bool(rc), done.value, taken.value, mean.value
+
+    def set_pixel_jitter(self, width: float = 1.0, on: bool = True) -> None:
+        """Anti-aliasing (include/pathtracer_amd.h, pt_renderer_set_pixel_jitter): while on,
+        every iteration enqueued sends each pixel's camera ray through a point drawn from a
+        ``width``-pixel square about the pixel's own point, per (iteration, pixel).  Host
+        state: before or after allocateOnGPU, between render calls, no synchronize needed.
+        Width 0 reproduces the unjittered render bit for bit."""
+        _err(lib().pt_renderer_set_pixel_jitter(self._h, 1 if on else 0, float(width)), "set_pixel_jitter")
+
+    def pixel_jitter(self):
+        """The current setting -> (on, width); (False, 1.0) until set."""
+        on, width = ctypes.c_int(), ctypes.c_float()
+        _err(lib().pt_renderer_pixel_jitter(self._h, ctypes.byref(on), ctypes.byref(width)), "pixel_jitter")
+        return bool(on.value), float(width.value)
 
     def free(self) -> None:
         if self._h:

@@ -371,6 +371,8 @@ int pt_renderer_render_adaptive(pt_renderer* r, int first_iter, int min_iters, i
     R_CALL(r->r->renderAdaptive(first_iter, min_iters, max_iters, check_every, tile_target, iters_done, pixel_samples,
                                 mean_err));
 }
+int pt_renderer_set_pixel_jitter(pt_renderer* r, int on, float width) { R_CALL(r->r->setPixelJitter(on, width)); }
+int pt_renderer_pixel_jitter(pt_renderer* r, int* on, float* width) { R_CALL(r->r->pixelJitter(on, width)); }
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;

@@ -3,7 +3,11 @@
 //
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
-//                  [--adaptive X [--check-every N] [--min-iter N]]
+//                  [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
+//
+// --jitter WIDTH: anti-aliasing (pt_renderer_set_pixel_jitter): every iteration's camera
+// rays go through a point drawn from a WIDTH-pixel square about the pixel's own point
+// (1 = the pixel's extent); works with every other option.
 //
 // --noise-target X: render until the mean relative noise estimate (pt_renderer_noise)
 // is at most X, checked every N iterations (default 32); --iter is then the most
@@ -34,7 +38,8 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
-                             "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]]\n", argv[0]);
+                             "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]] "
+                             "[--jitter WIDTH]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -48,6 +53,8 @@ int main(int argc, char** argv) {
     double adaptive_target = -1.0;       // >= 0: tile-based adaptive sampling
     int min_iter = 2;
     bool denoise = false;
+    bool jitter = false;
+    float jitter_width = 1.0f;
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
     for (int i = 2; i < argc; i++) {
@@ -62,6 +69,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--check-every") && i + 1 < argc) check_every = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) adaptive_target = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--min-iter") && i + 1 < argc) min_iter = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--jitter") && i + 1 < argc) { jitter = true; jitter_width = (float)std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
@@ -76,6 +84,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }
+    if (jitter && pt_renderer_set_pixel_jitter(r, 1, jitter_width) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     int iters = cfg.iterations;
     auto t0 = std::chrono::high_resolution_clock::now();
     if (adaptive_target >= 0) {

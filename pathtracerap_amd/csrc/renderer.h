@@ -180,6 +180,11 @@ public:
     int renderImageAdaptive(const std::string& path);
     int renderAdaptive(int first_iter, int min_iters, int max_iters, int check_every, double tile_target,
                        int* iters_done, long long* pixel_samples, double* mean_err);
+    // Pixel-jittered camera rays (anti-aliasing; no counterpart in the reference): while on, every
+    // iteration enqueued generates its camera rays through a per-(iteration, pixel) point of the
+    // pixel (k_gen_jitter) and traces them as bounce 1.  Host state; before or after allocateOnGPU
+    int setPixelJitter(int on, float width);
+    int pixelJitter(int* on, float* width) const;
 
     RenderConfig cfg;
     std::string last_error;
@@ -192,7 +197,9 @@ private:
     int allocPipe(KParams& k, size_t cap, hipStream_t st);
     int fail(hipError_t e, const char* what);
     void freeBuffers();
-    int enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask = nullptr);
+    int enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask = nullptr,
+                         bool jitter = false);
+    void launchGenJitter(const KParams& k, hipStream_t st, int iter, const unsigned char* tile_mask);
     int renderIters(int first_iter, int n_iters, const unsigned char* tile_mask, int* done_out);
     void launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, int iter, const unsigned char* tile_mask);
     int allocAdaptive();
@@ -242,6 +249,9 @@ private:
     unsigned char* mask_stage = nullptr;     // pinned host staging, kMaskSlots masks
     hipEvent_t mask_ev[kMaskSlots]{};        // slot i's upload has completed
     int mask_slot = 0;
+    bool jitter_on = false;              // setPixelJitter: the iterations enqueued from now on are jittered
+    float jitter_width = 1.0f;           // ... over this many pixels about the pixel's corner
+    bool jitter_sort1 = false;           // ray sort before a jittered iteration's bounce-1 trace too (PT_JITTER_SORT=1)
     int* tile_counts_dev = nullptr;      // adaptiveNoise / adaptiveMean: the counts, uploaded per call
     float* am_out = nullptr;             // adaptiveMean's result when the caller gives no device buffer
     int profiling = 0;

@@ -2710,6 +2710,73 @@ __global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, in
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
 
+// Bounce 0 of a pixel-jittered iteration (pt_renderer_set_pixel_jitter): one lane per
+// launched pixel writes its camera ray through a point of the pixel drawn from
+// (iteration, pixel), as bounce 0's survivor, into pool 0 -- nothing is intersected or
+// shaded here; bounce 1's trace finds the primary hit.  The two draws seed with depths
+// max_bounces + 1 and + 2, which shade() never uses (it seeds with 1 .. max_bounces),
+// and with the pixel index, so the offset does not depend on masks, pipelines or ranks.
+// Unmasked: every lane of a block emits, so the destination is the pixel index and the
+// block's count its pixel count.  MASKED: k_bounce_masked's per-lane tile byte and
+// ballot compaction; a pixel of an inactive tile emits nothing and writes contribution
+// 0.0.  Reads nothing but the mask; writes 48 bytes per emitted ray.
+template <int BS, bool MASKED>
+__global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float width,
+                                                    const unsigned char* __restrict__ tile_mask, int tiles_x) {
+    __shared__ int s_wave[MASKED ? BS / 64 : 1];
+    const int n = p.npix;
+    const int chunk = blockIdx.x;
+    const int j0 = chunk * BS;
+    if (j0 >= n) return;                       // whole block idle (uniform)
+    const int j = j0 + threadIdx.x;
+    const bool inside = j < n;
+    const int y = j / p.width, x = j - y * p.width;
+    bool active = inside;
+    int dst = j, total = min(BS, n - j0);
+    if (MASKED) {
+        if (inside) active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
+        if (inside && !active) {
+            float* cp = p.contrib + 3 * (size_t)j;
+            cp[0] = 0.0f;
+            cp[1] = 0.0f;
+            cp[2] = 0.0f;
+        }
+        const unsigned long long m = __ballot(active);
+        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        int base = 0;
+        total = 0;
+        if (BS > 64) {
+            if (lane == 0) s_wave[wid] = __popcll(m);
+            __syncthreads();
+        } else {
+            total = __popcll(m);
+        }
+#pragma unroll
+        for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
+            const int c = s_wave[w];
+            base += (w < wid) ? c : 0;
+            total += c;
+        }
+        dst = j0 + base + rank;
+    }
+    if (active) {
+        Rng rx = Rng::make(iter, j, p.max_bounces + 1);
+        Rng ry = Rng::make(iter, j, p.max_bounces + 2);
+        const float ux = rx.u01(), uy = ry.u01();
+        const float fx = (float)x + width * (ux - 0.5f);
+        const float fy = (float)y + width * (uy - 0.5f);
+        const float wx = (float)(p.plane_x0 + (double)(fx * p.step_x));
+        const float wy = (float)(p.plane_y0 + (double)(fy * p.step_y));
+        const f3 o = mk3(p.cam_x, p.cam_y, p.cam_z);
+        const f3 d = mk3(wx, wy, p.plane_z) - o;
+        p.ray[0][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(j));
+        p.ray[0][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(p.max_bounces));
+        p.ray[0][2][dst] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    }
+    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+}
+
 // One workgroup: exclusive scan of survivor counts of bounce `bounce`,
 // live count for bounce+1, and the first source block of every
 // destination block (dst_start).  A small workgroup with almost no LDS: it
@@ -3258,6 +3325,10 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     PT_HIP(hipStreamSynchronize(stream));
     const char* gr = std::getenv("PT_GRAPH");
     use_graph = gr && std::atoi(gr) != 0;
+    // jittered iterations: the generated rays are in pixel order already, and sorting them before
+    // the bounce-1 trace measured 1.3 % slower per iteration; 1 sorts them all the same
+    const char* js = std::getenv("PT_JITTER_SORT");
+    jitter_sort1 = js && std::atoi(js) != 0;
     allocated = true;
     cache_valid = false;
     return clearImage();
@@ -3422,6 +3493,46 @@ void Renderer::launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, i
     }
 }
 
+// Bounce 0 of a jittered iteration: one workgroup per compaction chunk of launched pixels
+// (the blocks k_scan(bounce 0) reads); tile_mask null: every tile emits.
+void Renderer::launchGenJitter(const KParams& k, hipStream_t st, int iter, const unsigned char* tile_mask) {
+    const int tx = noiseTilesX();
+    const float w = jitter_width;
+    const dim3 grid((unsigned)((k.npix + k.chunk - 1) / k.chunk));
+    switch (k.chunk) {
+        case 64:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<64, true>), grid, dim3(64), 0, st, k, iter, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_jitter<64, false>), grid, dim3(64), 0, st, k, iter, w, tile_mask, tx);
+            break;
+        case 128:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<128, true>), grid, dim3(128), 0, st, k, iter, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_jitter<128, false>), grid, dim3(128), 0, st, k, iter, w, tile_mask, tx);
+            break;
+        default:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<256, true>), grid, dim3(256), 0, st, k, iter, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_jitter<256, false>), grid, dim3(256), 0, st, k, iter, w, tile_mask, tx);
+            break;
+    }
+}
+
+int Renderer::setPixelJitter(int on, float width) {
+    if (!std::isfinite(width) || width < 0.0f) { last_error = "pixel jitter: width must be finite and >= 0"; return -1; }
+    // Rng::make keeps the depth in 9 bits of the seeding word; the draws use max_bounces + 1 and + 2
+    if (on && cfg.max_bounces + 2 > 511) {
+        last_error = "pixel jitter: max_bounces + 2 must not exceed 511 (the seeding word's depth field)";
+        return -1;
+    }
+    jitter_on = on != 0;
+    jitter_width = width;
+    return 0;
+}
+
+int Renderer::pixelJitter(int* on, float* width) const {
+    if (on) *on = jitter_on ? 1 : 0;
+    if (width) *width = jitter_width;
+    return 0;
+}
+
 // Bounce b's ray sort (when the pipeline sorts) and persistent trace launches, as
 // every iteration enqueues them (and the trace_rays test hook).  pall / ptrace: an
 // event pair around the sort kernels / around the trace launches only.
@@ -3450,21 +3561,35 @@ int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pal
 // scan per bounce.  iter = -1: k_bounce reads the id from k.iter_dev (capture).
 // tile_mask (device, never under capture): bounce 0 is k_bounce_masked; from bounce 1
 // on every kernel sizes its work from n_live, so nothing else differs.
-int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask) {
+// jitter (never under capture): bounce 0 is k_gen_jitter, which emits the camera rays
+// unshaded, so the first shade is bounce 1's and the iteration has one more pass,
+// b = 1 .. passes, each the ordinary sort / trace / shade / scan.  n_live (max_bounces + 4
+// entries) holds index passes + 1; k_scan stops counting segments per bounce at 64.
+int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask, bool jitter) {
     const KParams& k = pk[q];
     const dim3 grid((unsigned)kp.nblocks + 8u);
     // profiling 1: an event pair around every kernel group on every pipeline; 2: around the
     // trace phases of pipeline 0 only (cheap enough for a timed region: 1/16 of the pairs)
     const bool pall = profiling == 1, ptrace = pall || (profiling == 2 && q == 0);
+    if (jitter) passes++;
     for (int b = 0; b < passes; b++) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (b > 0 && split_trace) {
-            if (enqueueSortTrace(k, st, b, pall, ptrace) != 0) return -1;
+            if (b == 1 && jitter && !jitter_sort1 && k.order) {
+                // the generated rays are in pixel order: traced in claim order, unsorted (the
+                // result of a ray does not depend on who traces it; k_scan still clears the bins)
+                KParams ku = k;
+                ku.order = nullptr;
+                if (enqueueSortTrace(ku, st, b, pall, ptrace) != 0) return -1;
+            } else if (enqueueSortTrace(k, st, b, pall, ptrace) != 0) {
+                return -1;
+            }
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             launchBounce(k, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-            if (b == 0 && tile_mask) launchBounceMasked(k, st, grid, iter, tile_mask);
+            if (b == 0 && jitter) launchGenJitter(k, st, iter, tile_mask);
+            else if (b == 0 && tile_mask) launchBounceMasked(k, st, grid, iter, tile_mask);
             else launchBounce(k, st, b == 0, grid, iter, b, cfg.accel);
         }
         PT_HIP(hipGetLastError());
@@ -3519,6 +3644,9 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
         }
     }
     const int passes = cfg.max_bounces > 1 ? cfg.max_bounces : 1;
+    // jittered iterations are enqueued directly, like masked ones: never captured, never
+    // replayed, so the graphs of the plain loop stay valid across a switch
+    const bool jitter = jitter_on;
     const int np = npipes;
     if (np > 1) {                                   // fork the pipeline streams off the caller's stream
         PT_HIP(hipEventRecord(fork_ev, stream));
@@ -3533,7 +3661,7 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
         const int q = it % np;
         const KParams& k = pk[q];
         hipStream_t st = q == 0 ? stream : pstream[q];
-        if (use_graph && !profiling && st && !tile_mask) {   // (no capture on the legacy null stream)
+        if (use_graph && !profiling && st && !tile_mask && !jitter) {   // (no capture on the legacy null stream)
             // The bounce loop's launches are identical every iteration but for the
             // iteration id: capture them once per pipeline (k_bounce reads the id from
             // k.iter_dev) and replay the graph after one k_set_iter.
@@ -3551,7 +3679,7 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
                 PT_HIP(ei);
             }
             PT_HIP(hipGraphLaunch(gexec[q], st));
-        } else if (enqueueIteration(q, st, iter, passes, tile_mask) != 0) {
+        } else if (enqueueIteration(q, st, iter, passes, tile_mask, jitter) != 0) {
             return -1;
         }
         if (np > 1) {

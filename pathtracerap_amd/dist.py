@@ -27,7 +27,8 @@ def shard_iterations(total: int, rank: int, world: int) -> tuple[int, int]:
 
 
 def render_sharded(scene, cfg, total_iters: int, device=None,
-                   render_fn: Optional[Callable] = None, moments: bool = False):
+                   render_fn: Optional[Callable] = None, moments: bool = False,
+                   jitter: Optional[float] = None):
     """Render ``total_iters`` samples per pixel across the process group and
     return the summed accumulator (a (W*H*3,) float32 tensor on every rank).
 
@@ -41,6 +42,10 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
     ``Renderer.noise(total_iters)`` on the reduced buffers.  ``render_fn`` is
     then called as ``render_fn(first, n, image_tensor, m2_tensor)`` and
     ``noise`` is None.
+
+    ``jitter``: a width turns on pixel-jittered camera rays (Renderer.set_pixel_jitter)
+    on every rank; the offset depends on (iteration, pixel) only, so the shards add up
+    to the one-rank render.  None: unjittered.  Ignored with ``render_fn``.
     """
     import torch
     import torch.distributed as dist
@@ -65,6 +70,8 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
         r.bind_image(image.data_ptr(), keepalive=image)
         if moments:
             r.enable_moments(m2.data_ptr(), keepalive=m2)
+        if jitter is not None:
+            r.set_pixel_jitter(jitter)
         r.allocateOnGPU(scene)
         r.renderLoop(first_iter=first, n_iters=n, sync=False)
     if grouped:
