@@ -46,7 +46,8 @@ struct ModelRec {
     float reach;          // R: max over triangles of the (tolerance-grown) voxel-box diameter, model units
     int bvh4_root;        // index of the mesh's 4-wide BLAS root (Bvh4Node), -1: none (the 4-wide traces refuse it)
     float wdelta;         // tier-1 window: the walk is exact up to t_min + wdelta
-    float ivw[3];         // 1 / vw (rounded; walk certificate only, used with margins)
+    float ivw[3];         // 1 / vw (rounded; walk certificate only, used with margins); NaN where vw is 0:
+                          // no certificate for a mesh without extent on that axis
     float cslack[3];      // walk certificate: position slack per axis (DDA +EPSILON shift + rounding)
 };
 static_assert(sizeof(ModelRec) == 62 * 4, "ModelRec layout");

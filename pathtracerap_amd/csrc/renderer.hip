@@ -712,10 +712,14 @@ __device__ __forceinline__ bool walk_certify(const KParams& p, const ModelRec& M
     bool in0 = true;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        // the walk's start index is the exact one unless pt lies within the shift of an interior boundary
+        // the walk's start index is the exact one unless pt lies within the shift of an interior boundary.
+        // The three comparisons are written so that a NaN fails the condition: a mesh with no extent on
+        // axis a has voxel width 0 and ivw NaN there (Scene::buildDeviceTables), and its walk starts at the
+        // LAST voxel of that axis (|x + EPSILON| / 0 saturates) while its triangles sit in voxel 0 -- no
+        // position on the ray says where that walk goes, so every ray at such a mesh walks exactly
         const float q = (pp[a] - M.bbox[a]) * M.ivw[a];
         const float n = rintf(q);
-        if (n >= 1.0f && n <= (float)(p.gdim[a] - 1) && absr(q - n) * M.vw[a] <= M.cslack[a]) PT_CERT_FAIL(2)
+        if (!(n < 1.0f || n > (float)(p.gdim[a] - 1) || absr(q - n) * M.vw[a] > M.cslack[a])) PT_CERT_FAIL(2)
         v0[a] = min(max((int)floorf(q), 0), p.gdim[a] - 1);
         in0 = in0 && v0[a] >= ul[a] && v0[a] <= uh[a];
         const float lo = M.bbox[a] + (float)ul[a] * M.vw[a], hi = M.bbox[a] + (float)(uh[a] + 1) * M.vw[a];

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <sstream>
 
@@ -637,9 +638,15 @@ void Scene::buildDeviceTables() {
         // Walk certificate (renderer.hip walk_certify): position slack that covers the
         // DDA's +EPSILON initial-index shift and the rounding of its crossing
         // parameters (<= 26 rounded adds of positive steps, plus the initial
-        // (boundary - pt) * inv) relative to the exact ray, per axis.
+        // (boundary - pt) * inv) relative to the exact ray, per axis.  A mesh with no
+        // extent on axis k (a floor quad) has voxel width exactly 0 there: ivw is NaN,
+        // which makes walk_certify refuse every ray at it (the reference walk starts
+        // such a mesh at the last voxel of k and sees it from one side only; the exact
+        // walk reproduces that, no certificate does).  walk_certify_fast refuses it by
+        // its own `thick` test.
         for (int k = 0; k < 3; k++) {
-            r.ivw[k] = (float)(1.0 / (double)g.voxel_width[k]);
+            r.ivw[k] = g.voxel_width[k] > 0.0f ? (float)(1.0 / (double)g.voxel_width[k])
+                                               : std::numeric_limits<float>::quiet_NaN();
             const double span = (double)g.voxel_width[k] * grid_dim[k];
             const double mag = std::fabs((double)r.bbox[k]) + std::fabs((double)r.bbox[k + 3]) + span;
             r.cslack[k] = (float)(2.0 * kEps + 4.8e-7 * (grid_dim[k] + 4) * mag);

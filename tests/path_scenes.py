@@ -2,9 +2,11 @@
 trace and compaction paths that the scheduling tests never reach (deep
 traversal stacks, hit sets beyond LDS, grids other than 25^3, the model-count
 variants, empty meshes), and the named ray sets, direction scalings and
-survivor layouts that go through Renderer.trace_rays.  Test infrastructure:
-used by test_path_scenes.py (CPU preconditions), test_gpu_paths.py and
-test_gpu_trace_rays.py (GPU == oracle, bit for bit)."""
+survivor layouts that go through Renderer.trace_rays, and the flat meshes,
+exact ties and coincident instances of section I.  Test infrastructure: used by
+test_path_scenes.py and test_degenerate_cpu.py (CPU preconditions),
+test_gpu_paths.py, test_gpu_trace_rays.py and test_gpu_degenerate.py (GPU ==
+oracle, bit for bit)."""
 import numpy as np
 
 from helpers import assert_bitexact, flat_from_export, oracle_cfg
@@ -497,6 +499,341 @@ def layouts(n_slots, chunk, n, seed):
     return out
 
 
+# ---------------------------------------------------------------------------
+# I. flat meshes, exact ties, coincident instances
+# ---------------------------------------------------------------------------
+# Meshes with dyadic coordinates in the loaded (x1000) units, instanced at scale
+# 0.125 (a power of two), so model-space values are exact: a mesh with no extent
+# on a model axis gets a voxel width of exactly 0 there, a ray down onto the ridge
+# meets both roof sides at bit-equal t, two instances with one transform answer
+# at bit-equal distance.
+
+FLAT_HALF = 1024.0
+FLAT_THICKNESS = [0.0, 2.0 ** -7, 2.0 ** -2, 4.0]    # exactly flat; a voxel width far below, near, far above EPSILON
+FLAT_SCALE = 0.125
+FLAT_XFORM = dict(rot=(20, 30, 10), translate=(5, 7, 9))
+FLAT_RAYS = 4096
+
+
+def _unloaded(x):
+    """float32 OBJ-unit values v whose float32 product v * 1000 (what addMesh and
+    the oracle builder compute) is exactly the loaded-unit x."""
+    x = np.asarray(x, np.float64)
+    k = np.float32(1000)
+    v = (x / 1000.0).astype(np.float32)
+    up, down = v, v
+    for _ in range(3):                                  # the rounded quotient, else a neighbour a few ulps away
+        up, down = np.nextafter(up, np.float32(np.inf)), np.nextafter(down, np.float32(-np.inf))
+        for c in (up, down):
+            v = np.where(((v * k).astype(np.float64) != x) & ((c * k).astype(np.float64) == x), c, v)
+    assert ((v * k).astype(np.float64) == x).all(), "no float32 value loads to the dyadic coordinate"
+    return v.astype(np.float32)
+
+
+def flat_quad_mesh(axis, thickness=0.0):
+    """Two triangles, half-width FLAT_HALF on the two other axes; the coordinate on
+    `axis` is [0, 0, h, h] over the four corners (h = 0: no extent on that axis)."""
+    u, w = (axis + 1) % 3, (axis + 2) % 3
+    pos = np.zeros((4, 3), np.float64)
+    pos[:, u] = FLAT_HALF * np.array([-1, 1, 1, -1])
+    pos[:, w] = FLAT_HALF * np.array([-1, -1, 1, 1])
+    pos[:, axis] = [0.0, 0.0, thickness, thickness]
+    nrm = np.zeros((4, 3), np.float32)
+    nrm[:, axis] = 1.0
+    return _unloaded(pos), nrm, np.int32([(0, 1, 2), (0, 2, 3)])
+
+
+def needle_mesh():
+    """Two zero-area triangles on one line along x: the voxel widths on y and z are
+    0, and nothing can be hit."""
+    pos = np.zeros((4, 3), np.float64)
+    pos[:, 0] = [-FLAT_HALF, 0.0, FLAT_HALF, 512.0]
+    return _unloaded(pos), np.tile(np.float32([0, 1, 0]), (4, 1)), np.int32([(0, 1, 2), (1, 2, 3)])
+
+
+def flat_spec(axis, h, transformed=False, mesh=None):
+    """(meshes, models): one DIFFUSE instance of flat_quad_mesh(axis, h) (or `mesh`)
+    at scale FLAT_SCALE, untransformed otherwise or under FLAT_XFORM."""
+    x = FLAT_XFORM if transformed else dict(rot=(0, 0, 0), translate=(0, 0, 0))
+    return ([flat_quad_mesh(axis, h) if mesh is None else mesh],
+            [dict(mesh=0, scale=(FLAT_SCALE,) * 3, rot=x["rot"], translate=x["translate"], material="DIFFUSE",
+                  color=(0.7, 0.7, 0.7))])
+
+
+def flat_scene(P, axis, h, transformed=False):
+    """The product's scene of flat_spec, built once (degenerate_case's)."""
+    return degenerate_case(P, f"flat-{'xyz'[axis]}-{_h_id(h)}-{'xf' if transformed else 'id'}")[0]
+
+
+def flat_scene_oracle(O, axis, h, transformed=False):
+    """Its twin from the oracle's own builder."""
+    return oracle_scene_from_spec(O, *flat_spec(axis, h, transformed))
+
+
+def flat_axis(a, model=0):
+    """The model axis along which `model`'s mesh box is thinnest."""
+    bb = a["mesh_bbox"].reshape(-1, 6).astype(np.float64)[a["model_ints"][model, 0]]
+    return int(np.argmin(bb[3:] - bb[:3]))
+
+
+def model_dir(a, d, model=0):
+    """Model-space directions (float64) of world directions d."""
+    W = a["model_w2m"][model].reshape(4, 4).T.astype(np.float64)
+    return np.asarray(d, np.float64) @ W[:3, :3].T
+
+
+def flat_rays(a, n=FLAT_RAYS, seed=1):
+    """Rays at model 0, the flat quad: origins on both sides of its plane within 200
+    world units (at least 1 off it, so the direction's sign on the flat axis is
+    beyond rounding), targets uniform on the quad.  Under the identity rotation the
+    first eighth lie in the plane instead: origin in it, direction 0 on the flat
+    axis.  Returns (origins, directions, positive): `positive` marks the rays whose
+    model-space direction on the flat axis is > 0 (the in-plane rays are neither)."""
+    rs = np.random.RandomState(seed)
+    ax = flat_axis(a)
+    u, w = (ax + 1) % 3, (ax + 2) % 3
+    bb = a["mesh_bbox"].reshape(-1, 6).astype(np.float64)[a["model_ints"][0, 0]]
+    h = bb[3 + ax] - bb[ax]
+    M = m2w_of(a, 0)
+    identity = bool((M[:3, :3] == np.diag(np.diag(M[:3, :3]))).all())
+    tgt = np.zeros((n, 3))
+    tgt[:, u] = rs.uniform(-1, 1, n) * FLAT_HALF
+    tgt[:, w] = rs.uniform(-1, 1, n) * FLAT_HALF
+    tgt[:, ax] = h * (tgt[:, w] + FLAT_HALF) / (2 * FLAT_HALF)          # on the (tilted) quad
+    org = rs.uniform(-200, 200, (n, 3)) / FLAT_SCALE                     # model units
+    side = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    org[:, ax] = side * rs.uniform(1, 200, n) / FLAT_SCALE + (h if h > 0 else 0.0) * (side > 0)
+    inplane = np.zeros(n, bool)
+    if identity:
+        inplane[: n // 8] = True
+        org[inplane, ax] = 0.0
+        tgt[inplane, ax] = 0.0
+    o = to_world(a, 0, org).astype(np.float32)
+    d = (to_world(a, 0, tgt) - to_world(a, 0, org)).astype(np.float32)
+    if identity:                                                           # world == model / 8: exact zeros stay exact
+        d[inplane, ax] = 0.0
+        assert (model_dir(a, d)[inplane, ax] == 0).all()
+    dm = model_dir(a, d)[:, ax]
+    assert (np.abs(dm[~inplane]) > 1e-3 * np.abs(model_dir(a, d)).max(1)[~inplane]).all()
+    return o, d, dm > 0
+
+
+RIDGE_SEGMENTS = 64
+RIDGE_ORDERS = ["side-major", "reversed", "interleaved", "permuted"]
+RIDGE_PERM_SEED = 38         # the first seed that puts each side first on exactly half of the tie rays
+RIDGE_RAYS = 2048            # on the ridge, and as many controls off it: batches of 4096
+
+
+def _ridge_triangles(segments):
+    """(corners (4 s, 3, 3), side (4 s,)) of the roof in side-major order: the +z
+    side's strips along x, two triangles each, then the -z side's.  Ridge along x at
+    y = 1024, z = 0; eaves at y = 0, z = +-1024."""
+    xs = -FLAT_HALF + 2 * FLAT_HALF * np.arange(segments + 1) / segments
+    tris, side = [], []
+    for sg in (1.0, -1.0):
+        for i in range(segments):
+            A, B = (xs[i], 0.0, sg * FLAT_HALF), (xs[i + 1], 0.0, sg * FLAT_HALF)
+            C, D = (xs[i + 1], FLAT_HALF, 0.0), (xs[i], FLAT_HALF, 0.0)
+            tris += [(A, B, C), (A, C, D)]
+            side += [sg, sg]
+    return np.array(tris, np.float64), np.array(side)
+
+
+def ridge_order(order, segments=RIDGE_SEGMENTS):
+    """Permutation of the side-major triangles.  `interleaved`: strip by strip, the
+    +z side first in even strips and the -z side first in odd ones; `permuted`: a
+    seeded shuffle.  Both put each side first on exactly half of ridge_rays' tie
+    rays, so every pair of orders disagrees about the tie winner on at least half."""
+    n = 4 * segments
+    if order == "side-major":
+        return np.arange(n)
+    if order == "reversed":
+        return np.arange(n)[::-1].copy()
+    if order == "interleaved":
+        out = []
+        for i in range(segments):
+            p, m = [2 * i, 2 * i + 1], [2 * segments + 2 * i, 2 * segments + 2 * i + 1]
+            out += (p + m) if i % 2 == 0 else (m + p)
+        return np.array(out)
+    if order == "permuted":
+        return np.random.RandomState(RIDGE_PERM_SEED).permutation(n)
+    raise ValueError(order)
+
+
+def ridge_mesh(segments=RIDGE_SEGMENTS, order="side-major"):
+    """The roof, 4 * segments triangles with their own corners each, in `order`; the
+    vertex normals of a side are (0, 1, +-1): the hit normal's z sign names the side."""
+    tris, side = _ridge_triangles(segments)
+    perm = ridge_order(order, segments)
+    tris, side = tris[perm], side[perm]
+    nrm = np.zeros((len(tris), 3, 3), np.float32)
+    nrm[:, :, 1] = 1.0
+    nrm[:, :, 2] = side[:, None]
+    return _unloaded(tris.reshape(-1, 3)), nrm.reshape(-1, 3), np.arange(3 * len(tris), dtype=np.int32).reshape(-1, 3)
+
+
+def ridge_spec(order, segments=RIDGE_SEGMENTS):
+    return ([ridge_mesh(segments, order)],
+            [dict(mesh=0, scale=(FLAT_SCALE,) * 3, rot=(0, 0, 0), translate=(0, 0, 0), material="DIFFUSE",
+                  color=(0.7, 0.7, 0.7))])
+
+
+def ridge_scene(P, order):
+    return degenerate_case(P, f"ridge-{order}")[0]
+
+
+def _ridge_ray_x(n, segments=RIDGE_SEGMENTS):
+    """Model-space x of the n on-ridge rays: the first half at the strip boundaries
+    1..segments/2 (six triangles meet there: three of each side), the second half
+    inside every strip, at odd multiples of 2^-4 of its width."""
+    assert n % (2 * segments) == 0
+    wdt = 2 * FLAT_HALF / segments
+    nb = segments // 2
+    xb = -FLAT_HALF + wdt * (1 + np.arange(n // 2) % nb)
+    k = np.arange(n // 2)
+    xi = -FLAT_HALF + wdt * (k % segments + (2 * ((k // segments) % 8) + 1) / 16.0)
+    return np.concatenate([xb, xi])
+
+
+def ridge_rays(n=RIDGE_RAYS):
+    """World-space rays straight down, direction (0, -1, 0), from above the ridge of
+    ridge_scene: (origins on the ridge line, origins moved off it by +-2^-6 in z,
+    directions).  On the ridge both sides answer at the same t; off it they do not."""
+    x = _ridge_ray_x(n)
+    y = FLAT_HALF + 256.0 + 64.0 * (np.arange(n) % 5)
+    o = (np.c_[x, y, np.zeros(n)] * FLAT_SCALE).astype(np.float32)
+    off = o.copy()
+    off[:, 2] = np.where(np.arange(n) % 2 == 0, 1.0, -1.0) * 2.0 ** -6
+    d = np.tile(np.float32([0, -1, 0]), (n, 1))
+    return o, off, d
+
+
+def ridge_tie_sides(order, n=RIDGE_RAYS, segments=RIDGE_SEGMENTS):
+    """+1 / -1 per on-ridge ray: the side holding the lowest triangle index among
+    the triangles that touch the ray's ridge point, under `order`."""
+    x = _ridge_ray_x(n, segments)
+    perm = ridge_order(order, segments)
+    rank = np.empty(len(perm), int)
+    rank[perm] = np.arange(len(perm))                    # side-major triangle -> its index under `order`
+    wdt = 2 * FLAT_HALF / segments
+    s = (x + FLAT_HALF) / wdt
+    i = np.minimum(np.floor(s).astype(int), segments - 1)
+    best = {}
+    for sg, base in ((1.0, 0), (-1.0, 2 * segments)):
+        # strip i's second triangle holds the ridge edge; at a boundary the strip before it
+        # touches with both triangles (side-major indices base + 2 strip, + 1)
+        r = rank[base + 2 * i + 1]
+        atb = (s == i) & (i > 0)
+        j = np.maximum(i - 1, 0)
+        r = np.where(atb, np.minimum(r, np.minimum(rank[base + 2 * j], rank[base + 2 * j + 1])), r)
+        best[sg] = r
+    return np.where(best[1.0] < best[-1.0], 1.0, -1.0)
+
+
+COINCIDENT_K = [2, 10, 14]          # + the pair: 4, 12 and 16 models (LDS, wide and global model records)
+COINCIDENT_AT = ["first", "middle", "last"]
+_PAIR = dict(mesh=1, scale=(0.0625, 0.09375, 0.0625), rot=(15, 40, 5), translate=(30.0, 180.0, 60.0))
+
+
+def coincident_spec(k, where="middle", swapped=False):
+    """model_count_spec(k) plus two instances of its box mesh with one transform, a
+    DIFFUSE and a METAL one of different colours, adjacent at the start, the middle
+    or the end of the model order (`swapped`: the METAL one first).
+    Returns (meshes, models, index of the pair's first model)."""
+    meshes, models = model_count_spec(k)
+    pair = [dict(_PAIR, material="DIFFUSE", color=(0.9, 0.2, 0.2)), dict(_PAIR, material="METAL", color=(0.2, 0.9, 0.3))]
+    if swapped:
+        pair.reverse()
+    at = {"first": 0, "middle": len(models) // 2, "last": len(models)}[where]
+    models[at:at] = pair
+    return meshes, models, at
+
+
+def coincident_rays(n=FLAT_RAYS, seed=3):
+    """Half aimed at points in the pair's box from around the room, half random."""
+    rs = np.random.RandomState(seed)
+    o, d = random_rays(n, seed, center=(0.0, 200.0, 0.0), spread=450.0)
+    k = n // 2
+    tgt = np.array(_PAIR["translate"]) + rs.uniform(-40, 40, (k, 3))
+    d[:k] = (tgt - o[:k]).astype(np.float32)
+    return o, d
+
+
+def degenerate_room_spec():
+    """The synthetic room with a flat DIFFUSE floor quad (h = 0, seen from above), a
+    flat EMISSIVE quad turned to face down (its model-space y is the world's -y: the
+    grid sees it from below only) and a ridge."""
+    from pathtracerap_amd.synthetic import room_mesh
+    meshes = [room_mesh(), flat_quad_mesh(1, 0.0), ridge_mesh(RIDGE_SEGMENTS, "interleaved")]
+    models = [
+        dict(mesh=0, scale=(0.1, 0.1, 0.1), rot=(0, 0, 0), translate=(0, -120, 0), material="DIFFUSE", color=(0.85, 0.85, 0.85)),
+        dict(mesh=1, scale=(0.25, 0.25, 0.25), rot=(0, 0, 0), translate=(0, -112, 0), material="DIFFUSE", color=(0.3, 0.5, 0.9)),
+        dict(mesh=1, scale=(0.25, 0.25, 0.25), rot=(180, 0, 0), translate=(0, 800, -50), material="EMISSIVE",
+             color=(0.99, 0.99, 0.99)),
+        dict(mesh=2, scale=(0.125, 0.125, 0.125), rot=(0, 25, 0), translate=(40, -112, 60), material="DIFFUSE",
+             color=(0.9, 0.6, 0.2)),
+    ]
+    return meshes, models
+
+
+DEGENERATE_FRAME = dict(width=64, height=48, iterations=2, max_bounces=4)
+
+
+def _h_id(h):
+    return {0.0: "h0", 2.0 ** -7: "h2^-7", 2.0 ** -2: "h2^-2", 4.0: "h4"}[h]
+
+
+FLAT_NAMES = [f"flat-{'xyz'[ax]}-{_h_id(h)}-{x}" for ax in range(3) for h in FLAT_THICKNESS for x in ("id", "xf")]
+NEEDLE_NAMES = ["needle-id", "needle-xf"]
+RIDGE_NAMES = [f"ridge-{o}" for o in RIDGE_ORDERS]
+COINCIDENT_NAMES = [f"pair-{k}-{w}-{s}" for k in COINCIDENT_K for w in COINCIDENT_AT for s in ("ab", "ba")]
+DEGENERATE_NAMES = FLAT_NAMES + NEEDLE_NAMES + RIDGE_NAMES + COINCIDENT_NAMES
+
+
+def degenerate_spec(name):
+    """(meshes, models) of a named scene of section I."""
+    p = name.split("-")
+    if p[0] == "flat":
+        h = {_h_id(v): v for v in FLAT_THICKNESS}["-".join(p[2:-1])]
+        return flat_spec("xyz".index(p[1]), h, p[-1] == "xf")
+    if p[0] == "needle":
+        return flat_spec(0, 0.0, p[1] == "xf", mesh=needle_mesh())
+    if p[0] == "ridge":
+        return ridge_spec(name[len("ridge-"):])
+    if p[0] == "pair":
+        return coincident_spec(int(p[1]), p[2], p[3] == "ba")[:2]
+    raise ValueError(name)
+
+
+_DEGENERATE = {}
+
+
+def degenerate_case(P, name):
+    """(scene, origins, directions) of a named scene of section I and its rays, built
+    once: flat_rays for the flat quads and the needle, the on-ridge rays followed by
+    the off-ridge controls for the ridge, coincident_rays for the pairs."""
+    if name not in _DEGENERATE:
+        s = scene_once(("degenerate", name), lambda: scene_from_spec(P, *degenerate_spec(name)))
+        kind = name.split("-")[0]
+        if kind in ("flat", "needle"):
+            o, d, _ = flat_rays(s.export())
+        elif kind == "ridge":
+            on, off, d = ridge_rays()
+            o, d = np.concatenate([on, off]), np.concatenate([d, d])
+        else:
+            o, d = coincident_rays()
+        o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
+        assert np.isfinite(o).all() and np.isfinite(d).all() and (np.abs(d).max(1) > 0).all()
+        o.setflags(write=False); d.setflags(write=False)
+        _DEGENERATE[name] = (s, o, d)
+    return _DEGENERATE[name]
+
+
+def degenerate_oracle(P, O, name, accel):
+    s, o, d = degenerate_case(P, name)
+    return oracle_hits(O, ("degenerate", name), s, o, d, accel)
+
+
 _SCENES = {}
 
 
@@ -629,3 +966,23 @@ def check_render(P, O, key, scene, cfg, grid=(25, 25, 25), loops=None, what=""):
     assert seg == oseg, (what, seg, oseg)
     assert_bitexact(img, oimg, f"image {what}")
     return deferred, pipes
+
+
+def check_rays(r, scene, o, d, want, counts=None, what=""):
+    """trace_rays(o, d, counts) of renderer r == `want` (the oracle's dist, normal,
+    model of the same rays) == r.intersect_rays; returns trace_rays' result."""
+    ot, on, om = want
+    t, n, m, tri = r.trace_rays(o, d, counts)
+    assert r.trace_faults() == 0, what
+    assert_bitexact(m, om, f"model {what}")
+    assert_bitexact(t, ot, f"dist {what}")
+    hit = om >= 0
+    assert_bitexact(n[hit], on[hit], f"normal {what}")
+    t1, n1, m1 = r.intersect_rays(o, d)
+    assert_bitexact(m, m1, f"model vs intersect_rays {what}")
+    assert_bitexact(t, t1, f"dist vs intersect_rays {what}")
+    assert_bitexact(n, n1, f"normal vs intersect_rays {what}")
+    a = scene.export()
+    rng = a["mesh_ranges"][a["model_ints"][m[hit], 0]]
+    assert ((tri[hit] >= rng[:, 2]) & (tri[hit] < rng[:, 3])).all(), f"triangle outside the hit model's mesh {what}"
+    return t, n, m, tri

@@ -34,24 +34,7 @@ def _renderer(P, scene, accel, pipes, grid=G25, width=256, height=160, **kw):
     return r
 
 
-def _check(r, scene, o, d, want, counts=None, what=""):
-    """trace_rays(o, d, counts) of renderer r == `want` (the oracle's dist, normal,
-    model of the same rays) == r.intersect_rays; returns trace_rays' result."""
-    ot, on, om = want
-    t, n, m, tri = r.trace_rays(o, d, counts)
-    assert r.trace_faults() == 0, what
-    assert_bitexact(m, om, f"model {what}")
-    assert_bitexact(t, ot, f"dist {what}")
-    hit = om >= 0
-    assert_bitexact(n[hit], on[hit], f"normal {what}")
-    t1, n1, m1 = r.intersect_rays(o, d)
-    assert_bitexact(m, m1, f"model vs intersect_rays {what}")
-    assert_bitexact(t, t1, f"dist vs intersect_rays {what}")
-    assert_bitexact(n, n1, f"normal vs intersect_rays {what}")
-    a = scene.export()
-    rng = a["mesh_ranges"][a["model_ints"][m[hit], 0]]
-    assert ((tri[hit] >= rng[:, 2]) & (tri[hit] < rng[:, 3])).all(), f"triangle outside the hit model's mesh {what}"
-    return t, n, m, tri
+_check = S.check_rays
 
 
 def _first(want, k):
