@@ -104,6 +104,10 @@ struct KParams {
                                         // experiments); k_scan then counts a trace fault if any ray was deferred
     unsigned trace_iter_cap;            // persistent traces give up after this many loop iterations (a fault,
                                         // counted in segments[kTraceFaultCounter]); PT_TRACE_ITER_CAP overrides
+    int* slot_src;                      // ray sort: dense slot -> source index, written by k_sort_scatter for the
+                                        // shading pass of the same bounce; null: the pass searches blk_off
+                                        // (PT_SLOT_MAP=0, and every bounce whose trace ran unsorted).  Last, so
+                                        // the fields the trace kernels read keep their argument offsets
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
@@ -192,7 +196,7 @@ public:
 private:
     int launchPrimary();
     void launchTrace(const KParams& k, hipStream_t st, int b);
-    int enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace);
+    int enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace, bool host_rays);
     void launchBounce(const KParams& k, hipStream_t st, bool first, dim3 grid, int iter, int b, int accel);
     int allocPipe(KParams& k, size_t cap, hipStream_t st);
     int fail(hipError_t e, const char* what);
@@ -251,6 +255,7 @@ private:
     int mask_slot = 0;
     bool jitter_on = false;              // setPixelJitter: the iterations enqueued from now on are jittered
     float jitter_width = 1.0f;           // ... over this many pixels about the pixel's corner
+    bool slot_map = true;                // k_sort_scatter writes KParams::slot_src for the shading pass (PT_SLOT_MAP)
     bool jitter_sort1 = false;           // ray sort before a jittered iteration's bounce-1 trace too (PT_JITTER_SORT=1)
     int* tile_counts_dev = nullptr;      // adaptiveNoise / adaptiveMean: the counts, uploaded per call
     float* am_out = nullptr;             // adaptiveMean's result when the caller gives no device buffer

@@ -10,7 +10,8 @@
 //              k_trace_gf / k_trace_bvh -- persistent trace of every live slot
 //              into the hit buffer (k_trace_deferred: overflowed hit sets);
 //              k_bounce<rest, hitbuf> -- gather ray + hit (slot j -> source via
-//              the scan), shade, compact / accumulate
+//              the map the scatter wrote, else via the scan), shade, compact /
+//              accumulate
 //              (PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0: the fused k_bounce<rest, accel>)
 // Iterations run `pipelines` at a time on their own streams (Renderer::renderLoop);
 // with more than one, terminated rays write a per-pipeline contribution buffer
@@ -1179,15 +1180,14 @@ __device__ __forceinline__ void camera_ray(const KParams& p, int i, f3& o, f3& d
 struct RayState { f3 o, d, c; int pixel, bounces; };
 
 // shadeRayKernel (Renderer.cpp:411-479) for one ray; slot = iray.
-__device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& h, int iter, int slot) {
+// mt, mc: the hit model's material type and colour, read only for a hit of a ray with
+// bounces left (shade() loads them then; the hit-buffer pass has them loaded already).
+__device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, int slot, int mt, f3 mc) {
     if (r.bounces <= 0) r.c = r.c * mk3(0.01f, 0.01f, 0.01f);
     if (h.dist < kFMax) {
         const f3 dir = normalize(r.d);
         const f3 ip = r.o + dir * h.dist;
         if (r.bounces > 0) {
-            const ModelShade& S = p.shade[h.model];
-            const int mt = S.mat_type;
-            const f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
             if (mt == MAT_DIFFUSE || mt == MAT_METAL || mt == MAT_COAT) {
                 Rng rng = Rng::make(iter, slot, r.bounces);
                 if (mt == MAT_DIFFUSE) r.d = scatter_hemisphere(h.n, rng);
@@ -1212,6 +1212,17 @@ __device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& 
         return;
     }
     r.bounces--;
+}
+
+__device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& h, int iter, int slot) {
+    int mt = 0;
+    f3 mc = mk3(0, 0, 0);
+    if (h.dist < kFMax && r.bounces > 0) {
+        const ModelShade& S = p.shade[h.model];
+        mt = S.mat_type;
+        mc = mk3(S.color[0], S.color[1], S.color[2]);
+    }
+    shade_mat(r, h, iter, slot, mt, mc);
 }
 
 // ---------------------------------------------------------------------------
@@ -2538,7 +2549,7 @@ __global__ __launch_bounds__(BS) void k_trace_deferred(KParams p, int bounce) {
         atomicAdd(p.segments + kDeferredRayCounter, (unsigned long long)cnt);
     for (int q = blockIdx.x * BS + threadIdx.x; q < cnt; q += gridDim.x * BS) {
         const int j = p.defer_slots[q];
-        const int src = slot_source(p, j);
+        const int src = p.slot_src ? p.slot_src[j] : slot_source(p, j);   // this bounce's scatter ran before the trace
         const float4 a = p.ray[in_buf][0][src];
         const float4 b = p.ray[in_buf][1][src];
         float gdist;
@@ -2547,6 +2558,19 @@ __global__ __launch_bounds__(BS) void k_trace_deferred(KParams p, int bounce) {
                                                s_hs + threadIdx.x, gdist, gmodel, gtri);
         put_hit(p, j, gdist, gmodel, gtri);
     }
+}
+
+// The ray sort's key of a ray (defined with the sort kernels below).  PT_WRITER_KEYS: every
+// kernel that writes a surviving ray into a pool stores the key of the o and d it holds in
+// registers beside it, so k_sort_hist reads 2 bytes per ray instead of the two ray planes.
+// One key buffer per pipeline: bounce b's scatter has finished on the stream before
+// k_bounce(b) overwrites the keys.  0: k_sort_hist computes the keys (A/B builds).
+#ifndef PT_WRITER_KEYS
+#define PT_WRITER_KEYS 1
+#endif
+__device__ __forceinline__ int sort_key(const KParams& p, f3 o, f3 d);
+__device__ __forceinline__ void put_sort_key(const KParams& p, int dst, f3 o, f3 d) {
+    if (PT_WRITER_KEYS && p.sort_key) p.sort_key[dst] = (unsigned short)sort_key(p, o, d);
 }
 
 // One bounce for every live ray: gather -> intersect -> shade -> compact / accumulate.
@@ -2569,7 +2593,41 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
 
     RayState r;
     Hit h;
-    if (active) {
+    if (!FIRST && ACCEL == kAccelHitBuffer && p.slot_src) {     // a kernel argument: wave-uniform
+        // The sort of this bounce left slot j's source index in slot_src (k_sort_scatter), so
+        // the chain is two round trips: (slot_src, hit4, hitm)[j], which depend on j alone,
+        // then the ray planes, the triangle normal, the model's normal matrix and material.
+        if (active) {
+            const int src = p.slot_src[j];
+            const float4 hh = p.hit4[j];
+            const int hm = p.hitm[j];
+            const float4 a = p.ray[in_buf][0][src];
+            const float4 b = p.ray[in_buf][1][src];
+            const float4 c = p.ray[in_buf][2][src];
+            r.o = mk3(a.x, a.y, a.z); r.pixel = __float_as_int(a.w);
+            r.d = mk3(b.x, b.y, b.z); r.bounces = __float_as_int(b.w);
+            r.c = mk3(c.x, c.y, c.z);
+            // get_hit's values.  The second group's loads are unconditional, a miss's (and
+            // a hit without a triangle's) at index 0, which exists: a live ray at bounce >= 1
+            // means some triangle of some model was hit.  Under `if (hm >= 0)` the compiler
+            // sinks the load of hh.y into the branch: a third round trip.
+            const int tri = __float_as_int(hh.y);
+            const int mi = max(hm, 0);
+            const float4 tnl = p.tri_normal[max(tri, 0)];
+            float nm[9];
+#pragma unroll
+            for (int q = 0; q < 9; q++) nm[q] = p.models[mi].nm[q];
+            const ModelShade& S = p.shade[mi];
+            const int mt = S.mat_type;
+            const f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
+            const float4 tn = tri >= 0 ? tnl : make_float4(0, 0, 0, 0);
+            const f3 hn = normalize(xform_normal9(nm, mk3(tn.x, tn.y, tn.z)));
+            h.dist = hh.x;
+            h.model = hm;
+            h.n = hm >= 0 ? hn : mk3(0, 0, 0);
+            shade_mat(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc);
+        }
+    } else if (active) {
         if (FIRST) {
             camera_ray(p, j, r.o, r.d);
             r.c = mk3(1.0f, 1.0f, 1.0f);
@@ -2642,6 +2700,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
         p.ray[out_buf][0][dst] = make_float4(r.o.x, r.o.y, r.o.z, __int_as_float(r.pixel));
         p.ray[out_buf][1][dst] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(r.bounces));
         p.ray[out_buf][2][dst] = make_float4(r.c.x, r.c.y, r.c.z, 0.0f);
+        put_sort_key(p, dst, r.o, r.d);
     }
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
@@ -2710,6 +2769,7 @@ __global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, in
         p.ray[0][0][dst] = make_float4(r.o.x, r.o.y, r.o.z, __int_as_float(r.pixel));
         p.ray[0][1][dst] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(r.bounces));
         p.ray[0][2][dst] = make_float4(r.c.x, r.c.y, r.c.z, 0.0f);
+        put_sort_key(p, dst, r.o, r.d);
     }
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
@@ -2777,6 +2837,7 @@ __global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float wi
         p.ray[0][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(j));
         p.ray[0][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(p.max_bounces));
         p.ray[0][2][dst] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+        put_sort_key(p, dst, o, d);
     }
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
@@ -2918,6 +2979,10 @@ __device__ __forceinline__ int sort_key(const KParams& p, f3 o, f3 d) {
 
 // Rays entering bounce `bounce` sit at source index i = c*chunk + r (r < blk_cnt[c]) of
 // the previous bounce's pool; dense slot j = blk_off[c] + r.
+// COMPUTE: the keys are computed here from the ray planes and stored (rays the host
+// uploaded: the trace_rays hook; PT_WRITER_KEYS=0 builds); else the kernel that wrote
+// the rays left them in p.sort_key (put_sort_key).
+template <bool COMPUTE>
 __global__ __launch_bounds__(kSortWG) void k_sort_hist(KParams p, int bounce) {
     __shared__ int s_h[kSortBins];
     const int nprev = bounce == 1 ? p.npix : p.n_live[bounce - 1];
@@ -2933,10 +2998,15 @@ __global__ __launch_bounds__(kSortWG) void k_sort_hist(KParams p, int bounce) {
         if (i < lim) {
             const int c = i / p.chunk, r = i - c * p.chunk;
             if (r < p.blk_cnt[c]) {
-                const float4 a = p.ray[in_buf][0][i];
-                const float4 b = p.ray[in_buf][1][i];
-                const int key = sort_key(p, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z));
-                p.sort_key[i] = (unsigned short)key;
+                int key;
+                if (COMPUTE) {
+                    const float4 a = p.ray[in_buf][0][i];
+                    const float4 b = p.ray[in_buf][1][i];
+                    key = sort_key(p, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z));
+                    p.sort_key[i] = (unsigned short)key;
+                } else {
+                    key = p.sort_key[i];
+                }
                 atomicAdd(&s_h[key], 1);
             }
         }
@@ -3002,6 +3072,9 @@ __global__ __launch_bounds__(kSortWG) void k_sort_scatter(KParams p, int bounce)
         if (key[t] >= 0) {
             const int pos = s_h[key[t]] + rank[t];
             p.order[pos] = make_int2(jj[t], i0 + t * kSortWG + tid);
+            // the same pairing for this bounce's shading pass: jj rises with the source
+            // index inside a workgroup, so these stores are nearly coalesced
+            if (p.slot_src) p.slot_src[jj[t]] = i0 + t * kSortWG + tid;
         }
 }
 
@@ -3295,7 +3368,10 @@ int Renderer::allocateOnGPU(const Scene& scene) {
             kp.sort_sc[a] = ext > 0.0f && ext < 1e30f ? 16.0f / ext : 0.0f;
         }
     }
-    kp.order = nullptr; kp.sort_bins = nullptr; kp.sort_key = nullptr;
+    kp.order = nullptr; kp.sort_bins = nullptr; kp.sort_key = nullptr; kp.slot_src = nullptr;
+    // slot-to-source map for the shading pass of every sorted bounce (0: the pass searches blk_off)
+    const char* sm = std::getenv("PT_SLOT_MAP");
+    slot_map = sm ? std::atoi(sm) != 0 : true;
     PT_HIP(upload(allocs, &kp.segments, nullptr, (kDiagCounters + kMaxBounceCounters) * sizeof(unsigned long long), stream));
     PT_HIP(hipMemsetAsync(kp.segments, 0, (kDiagCounters + kMaxBounceCounters) * sizeof(unsigned long long), stream));
     // Pipelines: iterations in flight on their own streams, each with its own
@@ -3362,6 +3438,11 @@ int Renderer::allocPipe(KParams& k, size_t cap, hipStream_t st) {
     PT_HIP(hipMemsetAsync(k.defer_count, 0, sizeof(int), st));
     if (k.sort_mode) {
         PT_HIP(upload(allocs, &k.order, nullptr, cap * sizeof(int2), st));
+        if (slot_map) {
+            // zeroed: an entry no scatter wrote is read only by mistake, and then names pool slot 0
+            PT_HIP(upload(allocs, &k.slot_src, nullptr, cap * sizeof(int), st));
+            PT_HIP(hipMemsetAsync(k.slot_src, 0, cap * sizeof(int), st));
+        }
         PT_HIP(upload(allocs, &k.sort_key, nullptr, cap * sizeof(unsigned short), st));
         PT_HIP(upload(allocs, &k.sort_bins, nullptr, 2 * kSortBins * sizeof(int), st));
         PT_HIP(hipMemsetAsync(k.sort_bins, 0, 2 * kSortBins * sizeof(int), st));
@@ -3539,13 +3620,17 @@ int Renderer::pixelJitter(int* on, float* width) const {
 
 // Bounce b's ray sort (when the pipeline sorts) and persistent trace launches, as
 // every iteration enqueues them (and the trace_rays test hook).  pall / ptrace: an
-// event pair around the sort kernels / around the trace launches only.
-int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace) {
+// event pair around the sort kernels / around the trace launches only.  host_rays: the
+// pool was uploaded, not written by a kernel, so k_sort_hist computes the keys.
+// k.slot_src is set only together with k.order: the scatter launched here writes the map
+// the trace's deferred rays and the bounce's shading pass read.
+int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pall, bool ptrace, bool host_rays) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (k.order) {
         if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
         const dim3 sg((unsigned)((k.nblocks * (size_t)k.chunk + kSortWG * kSortPer - 1) / (kSortWG * kSortPer)));
-        hipLaunchKernelGGL(k_sort_hist, sg, dim3(kSortWG), 0, st, k, b);
+        if (host_rays || !PT_WRITER_KEYS) hipLaunchKernelGGL(k_sort_hist<true>, sg, dim3(kSortWG), 0, st, k, b);
+        else hipLaunchKernelGGL(k_sort_hist<false>, sg, dim3(kSortWG), 0, st, k, b);
         hipLaunchKernelGGL(k_sort_prefix, dim3(1), dim3(kSortWG), 0, st, k);
         hipLaunchKernelGGL(k_sort_scatter, sg, dim3(kSortWG), 0, st, k, b);
         if (pall) { hipEventRecord(e1, st); sort_events.push_back({e0, e1}); e0 = e1 = nullptr; }
@@ -3579,17 +3664,16 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, cons
     for (int b = 0; b < passes; b++) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (b > 0 && split_trace) {
-            if (b == 1 && jitter && !jitter_sort1 && k.order) {
-                // the generated rays are in pixel order: traced in claim order, unsorted (the
-                // result of a ray does not depend on who traces it; k_scan still clears the bins)
-                KParams ku = k;
-                ku.order = nullptr;
-                if (enqueueSortTrace(ku, st, b, pall, ptrace) != 0) return -1;
-            } else if (enqueueSortTrace(k, st, b, pall, ptrace) != 0) {
-                return -1;
-            }
+            // the generated rays of a jittered iteration are in pixel order: traced in claim
+            // order, unsorted (the result of a ray does not depend on who traces it; k_scan
+            // still clears the bins).  No scatter runs for that bounce, so its trace and its
+            // shading pass get no slot map either: slot_src would hold an earlier bounce's.
+            const bool unsorted = b == 1 && jitter && !jitter_sort1 && k.order;
+            KParams ku = k;
+            if (unsorted) { ku.order = nullptr; ku.slot_src = nullptr; }
+            if (enqueueSortTrace(ku, st, b, pall, ptrace, false) != 0) return -1;
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-            launchBounce(k, st, false, grid, iter, b, kAccelHitBuffer);
+            launchBounce(ku, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             if (b == 0 && jitter) launchGenJitter(k, st, iter, tile_mask);
@@ -3984,7 +4068,8 @@ int Renderer::traceRays(int n, const float* orig, const float* dir, const int* b
     PT_HIP(hipStreamSynchronize(stream));               // the host vectors are pageable
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanWG), 0, stream, k, 0);
     PT_HIP(hipGetLastError());
-    if (enqueueSortTrace(k, stream, 1, false, false) != 0) return -1;
+    // the keys an earlier render's kernels left belong to its rays, not to these
+    if (enqueueSortTrace(k, stream, 1, false, false, true) != 0) return -1;
     float* d_out = nullptr;                              // dist n, normal 3n, model n, tri n
     if (n > 0) {
         PT_HIP(hipMalloc(&d_out, (size_t)n * 24));
