@@ -409,6 +409,77 @@ int pt_renderer_render_adaptive(pt_renderer *r, int first_iter, int min_iters, i
 int pt_renderer_set_pixel_jitter(pt_renderer *r, int on, float width);
 /* The current setting (either pointer may be NULL); off and width 1.0 until set. */
 int pt_renderer_pixel_jitter(pt_renderer *r, int *on, float *width);
+
+/* ---- Free camera with a thin lens: look-at views and depth of field (added within ABI 9:
+ * new functions only, pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in
+ * the reference, whose generateRaysKernel looks down -z through one axis-aligned rectangle).
+ * Off by default: a renderer that never sets a camera allocates, launches and computes
+ * exactly what it did, through the config's legacy camera. ---- */
+typedef struct pt_camera {
+    float origin[3];              /* centre of the lens */
+    float p0[3];                  /* world point the ray of pixel coordinates (0, 0) goes through */
+    float du[3], dv[3];           /* world step per pixel in x and in y; the plane they span is the plane in focus */
+    float lens_u[3], lens_v[3];   /* two vectors spanning the lens (unit length for a round lens) */
+    float lens_radius;            /* 0: pinhole */
+} pt_camera;
+/* Sets the view of the iterations enqueued after the call; cam = NULL: back to the config's
+ * legacy camera.  The ray through pixel coordinates (fx, fy), for launched pixel p = y*W + x in
+ * iteration `it`, float32 IEEE in exactly this order, no fused multiply-add:
+ *   t_k = (p0_k + fx*du_k) + fy*dv_k                      k = x, y, z
+ *   pinhole:  o = origin
+ *   lens:     u1 = the first uniform of the reference's engine seeded (it, p, max_bounces + 3)
+ *             u2 = the first uniform of the engine seeded (it, p, max_bounces + 4)
+ *                  (two more depths the shading never seeds with; the index is the pixel)
+ *             rr = lens_radius * sqrtf(u1);  phi = 6.2831855f * u2
+ *             a = rr * cosf(phi);  b = rr * sinf(phi)     (the kernels' sinf / cosf, pt_selftest_math)
+ *             o_k = (origin_k + a*lens_u_k) + b*lens_v_k
+ *   direction = t - o (not normalised);  color = 1;  bounces = max_bounces
+ * (fx, fy) is ((float)x, (float)y) with the pixel jitter off and pt_renderer_set_pixel_jitter's
+ * x + width * (ux - 0.5f), y + width * (uy - 0.5f) with it on.
+ * Which iterations take which path.  A pinhole with the jitter off renders through the ordinary
+ * loop: the camera ray of bounce 0 takes the form above, and the primary-hit cache, tile masks,
+ * PT_GRAPH=1 replay and the denoiser's guides work as they do for the legacy camera.  With the
+ * jitter on or lens_radius > 0 an iteration is a jittered iteration: its rays are generated as
+ * bounce 0's survivors (with a lens and the jitter off the two jitter draws are not made), then
+ * come passes 1 .. max(max_bounces, 1); masks, the RNG slots, the segment accounting (the
+ * launched-pixel count more per iteration) and the direct enqueue under PT_GRAPH=1 are the
+ * jittered iteration's.
+ * The legacy-equivalent camera -- origin = cam, p0 = (plane_x0, plane_y0, plane_z),
+ * du = ((float)(plane_w / W), 0, 0), dv = (0, (float)(plane_h / H), 0) -- has the legacy camera's
+ * rays bit for bit, plain and jittered, whenever cam, plane_x0, plane_y0 and plane_z are
+ * float-representable (the default config's are).
+ * The primary-hit cache is always the hit of the pinhole ray through the pixel's own point.
+ * Limit: the denoiser's guides under a lens are thus the pinhole's, so a defocused pixel, a mix
+ * of surfaces, is filtered with the guides of the surface its centre ray hits.
+ * May be called before or after allocate_on_gpu.  After it the call is ordered on the renderer's
+ * stream after everything enqueued (no synchronize is needed between render calls and view
+ * changes; with PT_GRAPH=1 graphs in flight are waited for), invalidates the primary-hit cache,
+ * which the next render call rebuilds as the first one does, drops the captured graphs, and does
+ * what pt_renderer_clear_image does: a new view is a new render.
+ * Refused with a message before anything changes: a null renderer; "set_camera: every field must
+ * be finite"; "set_camera: du and dv must not be zero"; "set_camera: lens_radius must be >= 0";
+ * lens_radius > 0 when max_bounces + 4 > 511 (the seeding word's depth field). */
+int pt_renderer_set_camera(pt_renderer *r, const pt_camera *cam);
+/* The current view (out may be NULL): returns 1 when a camera is set, 0 for the legacy camera,
+ * for which *out receives the legacy-equivalent camera above. */
+int pt_renderer_camera(pt_renderer *r, pt_camera *out);
+/* A look-at view for a W x H frame (host only; computed in double, each field rounded once to
+ * float):  f = normalize(target - eye);  r = normalize(f x up);  u = r x f;
+ * hh = focus_dist * tan(vfov / 2);  hw = hh * W / H;  du = r * 2hw / W;  dv = u * 2hh / H;
+ * p0 = eye + f * focus_dist - r * hw - u * hh;  origin = eye;  lens_u = r;  lens_v = u.
+ * Pixel y grows along +u, as the legacy camera's grows along +y.  focus_dist places the plane in
+ * focus; for a pinhole it only scales du, dv and p0 along their rays.
+ * Refused: a null argument, a frame without pixels, a non-finite value, "look_at: eye and target
+ * coincide", "look_at: up is parallel to the view", "look_at: vfov_deg must lie in (0, 180)",
+ * "look_at: focus_dist must be > 0", "look_at: lens_radius must be >= 0". */
+int pt_camera_look_at(const double eye[3], const double target[3], const double up[3], double vfov_deg,
+                      double focus_dist, double lens_radius, int W, int H, pt_camera *out);
+/* The view the config file's RENDER block set, for a W x H frame: returns 1 and fills *out, or 0
+ * when the block set none (< 0: error).  Optional RENDER keys: camera_eye:[x,y,z] and
+ * camera_target:[x,y,z] (both or neither), camera_up:[x,y,z] (default [0,1,0]), camera_fov:DEG
+ * (vertical, default 45), camera_focus:D (default |target - eye|), camera_lens:R (default 0).
+ * pt_render and the command-line renderer apply it. */
+int pt_scene_camera(const pt_scene *s, int W, int H, pt_camera *out);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

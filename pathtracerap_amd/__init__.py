@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-__all__ = ["Scene", "Renderer", "RenderConfig", "PathTracerError", "build", "lib", "hw_queues",
+__all__ = ["Scene", "Renderer", "RenderConfig", "Camera", "look_at", "PathTracerError", "build", "lib", "hw_queues",
            "MATERIALS", "ACCEL_GRID", "ACCEL_BVH", "ACCEL_GRID_FAST"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,8 +70,15 @@ class _DenoiseParams(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int), ("sigma_l", ctypes.c_float), ("sigma_z", ctypes.c_float)]
 
 
+class _Camera(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_float * 3), ("p0", ctypes.c_float * 3), ("du", ctypes.c_float * 3),
+                ("dv", ctypes.c_float * 3), ("lens_u", ctypes.c_float * 3), ("lens_v", ctypes.c_float * 3),
+                ("lens_radius", ctypes.c_float)]
+
+
 _P_F = ctypes.POINTER(ctypes.c_float)
 _P_I = ctypes.POINTER(ctypes.c_int)
+_P_D = ctypes.POINTER(ctypes.c_double)
 _lib = None
 _HIP_BEFORE_LOAD = None     # set when the library loads (torch's HIP runtime already up?)
 
@@ -138,6 +145,11 @@ EXPORTS = [
                                                    ctypes.POINTER(ctypes.c_double)]),
     ("pt_renderer_set_pixel_jitter", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
     ("pt_renderer_pixel_jitter", ctypes.c_int, [ctypes.c_void_p, _P_I, _P_F]),
+    ("pt_renderer_set_camera", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera)]),
+    ("pt_renderer_camera", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera)]),
+    ("pt_camera_look_at", ctypes.c_int, [_P_D, _P_D, _P_D, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Camera)]),
+    ("pt_scene_camera", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Camera)]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -231,6 +243,50 @@ class RenderConfig:
         return c
 
 
+_CAMERA_VECS = ("origin", "p0", "du", "dv", "lens_u", "lens_v")
+
+
+@dataclass
+class Camera:
+    """pt_camera (include/pathtracer_amd.h): the free camera's lens centre, the world point
+    of pixel coordinates (0, 0), the world steps per pixel, which span the plane in focus,
+    and the lens's two spanning vectors and radius (0: a pinhole).  Values are float32."""
+    origin: tuple = (0.0, 0.0, 0.0)
+    p0: tuple = (0.0, 0.0, 0.0)
+    du: tuple = (1.0, 0.0, 0.0)
+    dv: tuple = (0.0, 1.0, 0.0)
+    lens_u: tuple = (1.0, 0.0, 0.0)
+    lens_v: tuple = (0.0, 1.0, 0.0)
+    lens_radius: float = 0.0
+
+    def c(self) -> _Camera:
+        c = _Camera()
+        for name in _CAMERA_VECS:
+            for k in range(3):
+                getattr(c, name)[k] = float(getattr(self, name)[k])
+        c.lens_radius = float(self.lens_radius)
+        return c
+
+    @classmethod
+    def from_c(cls, c: _Camera) -> "Camera":
+        return cls(*(tuple(float(v) for v in getattr(c, name)) for name in _CAMERA_VECS), float(c.lens_radius))
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0), vfov_deg: float = 45.0, focus_dist: float | None = None,
+            lens_radius: float = 0.0, width: int = 1000, height: int = 800) -> Camera:
+    """A look-at view for a ``width`` x ``height`` frame (pt_camera_look_at, which does the
+    arithmetic): the camera at ``eye`` looking at ``target``, a vertical field of view of
+    ``vfov_deg`` degrees, the plane in focus ``focus_dist`` away (None: at the target) and a
+    thin lens of ``lens_radius`` (0: a pinhole)."""
+    e, t, u = ((ctypes.c_double * 3)(*(float(v) for v in a)) for a in (eye, target, up))
+    if focus_dist is None:
+        focus_dist = float(np.sqrt(sum((float(t[k]) - float(e[k])) ** 2 for k in range(3))))
+    out = _Camera()
+    _err(lib().pt_camera_look_at(e, t, u, float(vfov_deg), float(focus_dist), float(lens_radius), int(width),
+                                 int(height), ctypes.byref(out)), "look_at")
+    return Camera.from_c(out)
+
+
 class Scene:
     """Scene (Scene.h:21-40).  ``Scene(config_path)`` parses a Config.txt
     grammar file; ``Scene()`` starts empty for programmatic construction."""
@@ -255,6 +311,13 @@ class Scene:
             c.width, c.height, c.iterations, c.max_bounces, c.accel)
         cfg.grid = tuple(c.grid)
         return cfg
+
+    def camera(self, width: int, height: int) -> Camera | None:
+        """The view the config's RENDER block set (camera_eye, camera_target, ...) for a
+        ``width`` x ``height`` frame, or None when it set none (pt_scene_camera)."""
+        out = _Camera()
+        rc = _err(lib().pt_scene_camera(self._h, int(width), int(height), ctypes.byref(out)), "scene camera")
+        return Camera.from_c(out) if rc > 0 else None
 
     def loadAndProcessMeshFile(self, path: str) -> int:
         return _err(lib().pt_scene_load_obj(self._h, os.fsencode(path)), f"load {path}")
@@ -601,6 +664,21 @@ class Renderer:
         on, width = ctypes.c_int(), ctypes.c_float()
         _err(lib().pt_renderer_pixel_jitter(self._h, ctypes.byref(on), ctypes.byref(width)), "pixel_jitter")
         return bool(on.value), float(width.value)
+
+    def set_camera(self, cam: Camera | None) -> None:
+        """A free view (include/pathtracer_amd.h, pt_renderer_set_camera) for the iterations
+        enqueued from now on; None: back to the config's legacy camera.  Before or after
+        allocateOnGPU; after it the call starts a new render (image, moments and sample counts
+        read zero) and needs no synchronize.  A pinhole with the jitter off keeps the ordinary
+        loop; a lens (``lens_radius`` > 0) or the jitter generates the rays per iteration."""
+        _err(lib().pt_renderer_set_camera(self._h, ctypes.byref(cam.c()) if cam is not None else None), "set_camera")
+
+    def camera(self):
+        """-> (is_set, Camera): the camera in use; for the legacy camera (False) the general
+        camera with the same rays."""
+        out = _Camera()
+        rc = _err(lib().pt_renderer_camera(self._h, ctypes.byref(out)), "camera")
+        return bool(rc), Camera.from_c(out)
 
     def free(self) -> None:
         if self._h:

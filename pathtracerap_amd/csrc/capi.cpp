@@ -1,4 +1,5 @@
 // capi.cpp -- extern "C" boundary (include/pathtracer_amd.h).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -373,6 +374,79 @@ int pt_renderer_render_adaptive(pt_renderer* r, int first_iter, int min_iters, i
 }
 int pt_renderer_set_pixel_jitter(pt_renderer* r, int on, float width) { R_CALL(r->r->setPixelJitter(on, width)); }
 int pt_renderer_pixel_jitter(pt_renderer* r, int* on, float* width) { R_CALL(r->r->pixelJitter(on, width)); }
+static_assert(sizeof(pt_camera) == sizeof(pt::CameraRec), "pt_camera and pt::CameraRec share one layout");
+int pt_renderer_set_camera(pt_renderer* r, const pt_camera* cam) {
+    pt::CameraRec c;
+    if (cam) std::memcpy(&c, cam, sizeof c);
+    R_CALL(r->r->setCamera(cam ? &c : nullptr));
+}
+int pt_renderer_camera(pt_renderer* r, pt_camera* out) {
+    if (!r || !r->r) return set_err("null renderer");
+    pt::CameraRec c;
+    const int rc = r->r->camera(&c);
+    if (out) std::memcpy(out, &c, sizeof c);
+    return rc;
+}
+
+int pt_camera_look_at(const double eye[3], const double target[3], const double up[3], double vfov_deg,
+                      double focus_dist, double lens_radius, int W, int H, pt_camera* out) {
+    if (!eye || !target || !up || !out) return set_err("look_at: null argument");
+    if (W <= 0 || H <= 0) return set_err("look_at: bad resolution");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(eye[k]) || !std::isfinite(target[k]) || !std::isfinite(up[k]))
+            return set_err("look_at: every value must be finite");
+    if (!std::isfinite(vfov_deg) || !std::isfinite(focus_dist) || !std::isfinite(lens_radius))
+        return set_err("look_at: every value must be finite");
+    auto norm = [](const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    auto cross = [](const double a[3], const double b[3], double o[3]) {
+        o[0] = a[1] * b[2] - a[2] * b[1];
+        o[1] = a[2] * b[0] - a[0] * b[2];
+        o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double f[3] = {target[0] - eye[0], target[1] - eye[1], target[2] - eye[2]};
+    const double fl = norm(f);
+    if (!(fl > 0.0)) return set_err("look_at: eye and target coincide");
+    for (int k = 0; k < 3; k++) f[k] /= fl;
+    const double ul = norm(up);
+    double r[3], u[3];
+    cross(f, up, r);
+    const double rl = norm(r);
+    // |f x up| = |up| sin(angle): parallel to within rounding counts as parallel
+    if (!(ul > 0.0) || !(rl > 1e-12 * ul)) return set_err("look_at: up is parallel to the view");
+    for (int k = 0; k < 3; k++) r[k] /= rl;
+    cross(r, f, u);
+    if (!(vfov_deg > 0.0 && vfov_deg < 180.0)) return set_err("look_at: vfov_deg must lie in (0, 180)");
+    if (!(focus_dist > 0.0)) return set_err("look_at: focus_dist must be > 0");
+    if (lens_radius < 0.0) return set_err("look_at: lens_radius must be >= 0");
+    const double hh = focus_dist * std::tan(vfov_deg * (3.14159265358979323846 / 180.0) * 0.5);
+    const double hw = hh * (double)W / (double)H;
+    for (int k = 0; k < 3; k++) {
+        out->origin[k] = (float)eye[k];
+        out->p0[k] = (float)(eye[k] + f[k] * focus_dist - r[k] * hw - u[k] * hh);
+        out->du[k] = (float)(r[k] * (2.0 * hw / (double)W));
+        out->dv[k] = (float)(u[k] * (2.0 * hh / (double)H));
+        out->lens_u[k] = (float)r[k];
+        out->lens_v[k] = (float)u[k];
+    }
+    out->lens_radius = (float)lens_radius;
+    return 0;
+}
+
+int pt_scene_camera(const pt_scene* s, int W, int H, pt_camera* out) {
+    if (!s || !out) return set_err("null argument");
+    const pt::RenderSettings& st = s->s.settings;
+    if (!st.has_camera) return 0;
+    double focus = st.cam_focus;
+    if (focus < 0.0) {
+        double d2 = 0.0;
+        for (int k = 0; k < 3; k++) d2 += (st.cam_target[k] - st.cam_eye[k]) * (st.cam_target[k] - st.cam_eye[k]);
+        focus = std::sqrt(d2);
+        if (!(focus > 0.0)) return set_err("look_at: eye and target coincide");
+    }
+    if (pt_camera_look_at(st.cam_eye, st.cam_target, st.cam_up, st.cam_fov, focus, st.cam_lens, W, H, out) < 0) return -1;
+    return 1;
+}
+
 void pt_renderer_free(pt_renderer* r) {
     if (!r) return;
     delete r->r;
@@ -396,6 +470,10 @@ int pt_render(const char* scene_config, const pt_render_config* cfg, const char*
     if (rc >= 0) rc = pt_scene_build(s, c.grid, c.accel != PT_ACCEL_GRID ? 1 : 0);
     pt_renderer* r = rc >= 0 ? pt_renderer_create(&c) : nullptr;
     if (rc >= 0 && !r) rc = -1;
+    pt_camera cam;
+    const int has_cam = rc >= 0 ? pt_scene_camera(s, c.width, c.height, &cam) : 0;
+    if (has_cam < 0) rc = -1;
+    if (rc >= 0 && has_cam > 0) rc = pt_renderer_set_camera(r, &cam);
     if (rc >= 0) rc = pt_renderer_allocate_on_gpu(r, s);
     if (rc >= 0) rc = pt_renderer_render_loop(r, 0, c.iterations);
     if (rc >= 0) rc = pt_renderer_synchronize(r);

@@ -4,6 +4,13 @@
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
 //                  [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
+//                  [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] [--focus D] [--lens R]]
+//
+// --look-from / --look-at: a free camera (pt_camera_look_at, pt_renderer_set_camera) at the
+// first point looking at the second, with --up (default 0 1 0), a vertical field of view of
+// --fov degrees (default 45), the plane in focus --focus away (default the distance between
+// the two points) and a thin lens of radius --lens (default 0: a pinhole, everything sharp).
+// Without them the scene file's camera_* keys apply, and without those the legacy camera.
 //
 // --jitter WIDTH: anti-aliasing (pt_renderer_set_pixel_jitter): every iteration's camera
 // rays go through a point drawn from a WIDTH-pixel square about the pixel's own point
@@ -25,6 +32,7 @@
 // Default: PT_ACCEL_GRID_FAST (the reference grid's image, bit for bit) with 16
 // iterations in flight, each on its own HIP stream and hardware queue.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,7 +47,8 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
                              "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]] "
-                             "[--jitter WIDTH]\n", argv[0]);
+                             "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
+                             "[--focus D] [--lens R]]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -55,6 +64,10 @@ int main(int argc, char** argv) {
     bool denoise = false;
     bool jitter = false;
     float jitter_width = 1.0f;
+    bool has_from = false, has_at = false, has_focus = false, cam_opt = false;
+    double eye[3] = {0, 0, 0}, target[3] = {0, 0, 0}, up[3] = {0, 1, 0};
+    double fov = 45.0, focus = 0.0, lens = 0.0;       // no --focus: the distance from eye to target
+    auto vec3 = [&](double* v, int& i) { for (int k = 0; k < 3; k++) v[k] = std::atof(argv[++i]); };
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
     for (int i = 2; i < argc; i++) {
@@ -70,6 +83,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) adaptive_target = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--min-iter") && i + 1 < argc) min_iter = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--jitter") && i + 1 < argc) { jitter = true; jitter_width = (float)std::atof(argv[++i]); }
+        else if (!std::strcmp(argv[i], "--look-from") && i + 3 < argc) { vec3(eye, i); has_from = true; }
+        else if (!std::strcmp(argv[i], "--look-at") && i + 3 < argc) { vec3(target, i); has_at = true; }
+        else if (!std::strcmp(argv[i], "--up") && i + 3 < argc) { vec3(up, i); cam_opt = true; }
+        else if (!std::strcmp(argv[i], "--fov") && i + 1 < argc) { fov = std::atof(argv[++i]); cam_opt = true; }
+        else if (!std::strcmp(argv[i], "--focus") && i + 1 < argc) { focus = std::atof(argv[++i]); has_focus = cam_opt = true; }
+        else if (!std::strcmp(argv[i], "--lens") && i + 1 < argc) { lens = std::atof(argv[++i]); cam_opt = true; }
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
@@ -78,12 +97,30 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--adaptive excludes --noise-target and --denoise\n");
         return 2;
     }
+    if (has_from != has_at || (cam_opt && !has_from)) {
+        std::fprintf(stderr, "a camera needs both --look-from and --look-at\n");
+        return 2;
+    }
+    pt_camera cam;
+    int has_cam = 0;
+    if (has_from) {
+        if (!has_focus) {
+            double d2 = 0;
+            for (int k = 0; k < 3; k++) d2 += (target[k] - eye[k]) * (target[k] - eye[k]);
+            focus = std::sqrt(d2);
+        }
+        has_cam = pt_camera_look_at(eye, target, up, fov, focus, lens, cfg.width, cfg.height, &cam) < 0 ? -1 : 1;
+    } else {
+        has_cam = pt_scene_camera(s, cfg.width, cfg.height, &cam);
+    }
+    if (has_cam < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
     if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }
+    if (has_cam > 0 && pt_renderer_set_camera(r, &cam) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     if (jitter && pt_renderer_set_pixel_jitter(r, 1, jitter_width) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     int iters = cfg.iterations;
     auto t0 = std::chrono::high_resolution_clock::now();

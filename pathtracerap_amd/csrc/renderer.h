@@ -33,6 +33,17 @@ struct RenderConfig {            // Config.h + generateRaysKernel constants, at 
     double plane_x0 = -10.0, plane_y0 = -4.0, plane_w = 20.0, plane_h = 16.0;  // Renderer.cpp:538-542
 };
 
+// The free camera (pt_camera, include/pathtracer_amd.h; no counterpart in the reference): one
+// device record per renderer behind KParams::camera, written by k_set_camera on the renderer's
+// stream.  The same layout as pt_camera.
+struct CameraRec {
+    float origin[3];            // centre of the lens
+    float p0[3];                // world point of pixel coordinates (0, 0)
+    float du[3], dv[3];         // world step per pixel in x and in y
+    float lens_u[3], lens_v[3]; // the lens's two spanning vectors
+    float lens_radius;          // 0: pinhole
+};
+
 // Everything a kernel needs, passed by value as the kernel argument.
 struct KParams {
     // scene (read-only, stays L2/MALL resident)
@@ -106,8 +117,10 @@ struct KParams {
                                         // counted in segments[kTraceFaultCounter]); PT_TRACE_ITER_CAP overrides
     int* slot_src;                      // ray sort: dense slot -> source index, written by k_sort_scatter for the
                                         // shading pass of the same bounce; null: the pass searches blk_off
-                                        // (PT_SLOT_MAP=0, and every bounce whose trace ran unsorted).  Last, so
-                                        // the fields the trace kernels read keep their argument offsets
+                                        // (PT_SLOT_MAP=0, and every bounce whose trace ran unsorted).  After the
+                                        // fields the trace kernels read, so those keep their argument offsets
+    const CameraRec* camera;            // setCamera: the free camera camera_ray and k_gen_camera read; null: the
+                                        // config's legacy camera (cam_*, plane_*, step_*).  Last, for the same reason
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
@@ -189,6 +202,12 @@ public:
     // pixel (k_gen_jitter) and traces them as bounce 1.  Host state; before or after allocateOnGPU
     int setPixelJitter(int on, float width);
     int pixelJitter(int* on, float* width) const;
+    // Free camera with a thin lens (no counterpart in the reference): null = the config's legacy
+    // camera.  A pinhole with the jitter off renders through the ordinary loop (camera_ray takes the
+    // general form); a lens or the jitter generates the rays (k_gen_camera) and traces them as bounce
+    // 1.  Before or after allocateOnGPU; after it, a new view starts a new render
+    int setCamera(const CameraRec* cam);
+    int camera(CameraRec* out) const;                // 1: a camera is set; 0: legacy (out = its equivalent)
 
     RenderConfig cfg;
     std::string last_error;
@@ -204,6 +223,7 @@ private:
     int enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask = nullptr,
                          bool jitter = false);
     void launchGenJitter(const KParams& k, hipStream_t st, int iter, const unsigned char* tile_mask);
+    void launchGenCamera(const KParams& k, hipStream_t st, int iter, const unsigned char* tile_mask);
     int renderIters(int first_iter, int n_iters, const unsigned char* tile_mask, int* done_out);
     void launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, int iter, const unsigned char* tile_mask);
     int allocAdaptive();
@@ -255,6 +275,9 @@ private:
     int mask_slot = 0;
     bool jitter_on = false;              // setPixelJitter: the iterations enqueued from now on are jittered
     float jitter_width = 1.0f;           // ... over this many pixels about the pixel's corner
+    bool camera_on = false;              // setCamera: cam_rec holds the view; kp.camera / pk[].camera point at cam_dev
+    CameraRec cam_rec{};
+    CameraRec* cam_dev = nullptr;        // the device record (allocateOnGPU)
     bool slot_map = true;                // k_sort_scatter writes KParams::slot_src for the shading pass (PT_SLOT_MAP)
     bool jitter_sort1 = false;           // ray sort before a jittered iteration's bounce-1 trace too (PT_JITTER_SORT=1)
     int* tile_counts_dev = nullptr;      // adaptiveNoise / adaptiveMean: the counts, uploaded per call

@@ -1168,9 +1168,23 @@ __device__ Hit intersect_scene(const KParams& p, f3 orig, f3 dir, int* stack, in
     return make_hit(p, gdist, gmodel, gtri);
 }
 
-// generateRaysKernel (Renderer.cpp:521-555)
+// The free camera's point of pixel coordinates (fx, fy): (p0 + fx*du) + fy*dv per coordinate,
+// products rounded before the adds (pt_camera, include/pathtracer_amd.h).
+__device__ __forceinline__ f3 camera_point(const CameraRec& c, float fx, float fy) {
+    return mk3((c.p0[0] + fx * c.du[0]) + fy * c.dv[0], (c.p0[1] + fx * c.du[1]) + fy * c.dv[1],
+               (c.p0[2] + fx * c.du[2]) + fy * c.dv[2]);
+}
+
+// generateRaysKernel (Renderer.cpp:521-555); with a camera set (p.camera, a kernel argument:
+// wave-uniform) the pinhole ray of the free camera through the pixel's own point.
 __device__ __forceinline__ void camera_ray(const KParams& p, int i, f3& o, f3& d) {
     const int y = i / p.width, x = i % p.width;
+    if (p.camera) {
+        const CameraRec& c = *p.camera;
+        o = mk3(c.origin[0], c.origin[1], c.origin[2]);
+        d = camera_point(c, (float)x, (float)y) - o;
+        return;
+    }
     const float wx = (float)(p.plane_x0 + (double)((float)x * p.step_x));
     const float wy = (float)(p.plane_y0 + (double)((float)y * p.step_y));
     o = mk3(p.cam_x, p.cam_y, p.cam_z);
@@ -2842,6 +2856,93 @@ __global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float wi
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
 
+// k_gen_jitter for the free camera (pt_renderer_set_camera): bounce 0 of an iteration whose
+// rays are generated because the pixel jitter is on (jit, a kernel argument: wave-uniform)
+// or the camera has a lens (lens_radius > 0, a uniform load).  The point of the plane in
+// focus is camera_point(fx, fy), with k_gen_jitter's (fx, fy) under the jitter and the
+// pixel's own (x, y) without it (no draw is made then); a lens moves the origin to a point
+// of its disc drawn from depths max_bounces + 3 and + 4, two more that shade() never seeds
+// with, and the pixel index.  The block layout, the mask and the compaction are
+// k_gen_jitter's, which keeps its own code for the legacy camera.
+template <int BS, bool MASKED>
+__global__ __launch_bounds__(BS) void k_gen_camera(KParams p, int iter, int jit, float width,
+                                                    const unsigned char* __restrict__ tile_mask, int tiles_x) {
+    __shared__ int s_wave[MASKED ? BS / 64 : 1];
+    const int n = p.npix;
+    const int chunk = blockIdx.x;
+    const int j0 = chunk * BS;
+    if (j0 >= n) return;                       // whole block idle (uniform)
+    const int j = j0 + threadIdx.x;
+    const bool inside = j < n;
+    const int y = j / p.width, x = j - y * p.width;
+    bool active = inside;
+    int dst = j, total = min(BS, n - j0);
+    if (MASKED) {
+        if (inside) active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
+        if (inside && !active) {
+            float* cp = p.contrib + 3 * (size_t)j;
+            cp[0] = 0.0f;
+            cp[1] = 0.0f;
+            cp[2] = 0.0f;
+        }
+        const unsigned long long m = __ballot(active);
+        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        int base = 0;
+        total = 0;
+        if (BS > 64) {
+            if (lane == 0) s_wave[wid] = __popcll(m);
+            __syncthreads();
+        } else {
+            total = __popcll(m);
+        }
+#pragma unroll
+        for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
+            const int c = s_wave[w];
+            base += (w < wid) ? c : 0;
+            total += c;
+        }
+        dst = j0 + base + rank;
+    }
+    if (active) {
+        const CameraRec& c = *p.camera;
+        float fx = (float)x, fy = (float)y;
+        if (jit) {
+            Rng rx = Rng::make(iter, j, p.max_bounces + 1);
+            Rng ry = Rng::make(iter, j, p.max_bounces + 2);
+            const float ux = rx.u01(), uy = ry.u01();
+            fx = (float)x + width * (ux - 0.5f);
+            fy = (float)y + width * (uy - 0.5f);
+        }
+        const f3 t = camera_point(c, fx, fy);
+        f3 o = mk3(c.origin[0], c.origin[1], c.origin[2]);
+        if (c.lens_radius > 0.0f) {
+            Rng r1 = Rng::make(iter, j, p.max_bounces + 3);
+            Rng r2 = Rng::make(iter, j, p.max_bounces + 4);
+            const float u1 = r1.u01(), u2 = r2.u01();
+            const float rr = c.lens_radius * sqrtf(u1);
+            const float phi = kTwoPi * u2;
+            float sp, cp;
+            sincos_ref(phi, &sp, &cp);
+            const float a = rr * cp, b = rr * sp;
+            o = mk3((c.origin[0] + a * c.lens_u[0]) + b * c.lens_v[0], (c.origin[1] + a * c.lens_u[1]) + b * c.lens_v[1],
+                    (c.origin[2] + a * c.lens_u[2]) + b * c.lens_v[2]);
+        }
+        const f3 d = t - o;
+        p.ray[0][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(j));
+        p.ray[0][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(p.max_bounces));
+        p.ray[0][2][dst] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+        put_sort_key(p, dst, o, d);
+    }
+    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+}
+
+// pt_renderer_set_camera after allocate_on_gpu: the new view, by value, into the renderer's
+// device record, ordered on its stream like any kernel.
+__global__ void k_set_camera(CameraRec* dst, CameraRec c) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = c;
+}
+
 // One workgroup: exclusive scan of survivor counts of bounce `bounce`,
 // live count for bounce+1, and the first source block of every
 // destination block (dst_start).  A small workgroup with almost no LDS: it
@@ -3266,6 +3367,9 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     const size_t cap = (size_t)kp.nblocks * kp.chunk;
     PT_HIP(upload(allocs, &kp.cache_hit, nullptr, cap * sizeof(float4), stream));
     PT_HIP(upload(allocs, &kp.cache_model, nullptr, cap * sizeof(int), stream));
+    // the free camera's record (setCamera); kernels see it only while a camera is set
+    PT_HIP(upload(allocs, &cam_dev, &cam_rec, sizeof(CameraRec), stream));
+    kp.camera = camera_on ? cam_dev : nullptr;
     if (external_image) kp.image = ext_image;
     else PT_HIP(upload(allocs, &kp.image, nullptr, (size_t)npix_all * 3 * sizeof(float), stream));
     {
@@ -3600,6 +3704,87 @@ void Renderer::launchGenJitter(const KParams& k, hipStream_t st, int iter, const
     }
 }
 
+// k_gen_jitter's launch for the free camera: the jitter state rides along as an argument
+void Renderer::launchGenCamera(const KParams& k, hipStream_t st, int iter, const unsigned char* tile_mask) {
+    const int tx = noiseTilesX();
+    const int jit = jitter_on ? 1 : 0;
+    const float w = jitter_width;
+    const dim3 grid((unsigned)((k.npix + k.chunk - 1) / k.chunk));
+    switch (k.chunk) {
+        case 64:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<64, true>), grid, dim3(64), 0, st, k, iter, jit, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_camera<64, false>), grid, dim3(64), 0, st, k, iter, jit, w, tile_mask, tx);
+            break;
+        case 128:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<128, true>), grid, dim3(128), 0, st, k, iter, jit, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_camera<128, false>), grid, dim3(128), 0, st, k, iter, jit, w, tile_mask, tx);
+            break;
+        default:
+            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<256, true>), grid, dim3(256), 0, st, k, iter, jit, w, tile_mask, tx);
+            else hipLaunchKernelGGL((k_gen_camera<256, false>), grid, dim3(256), 0, st, k, iter, jit, w, tile_mask, tx);
+            break;
+    }
+}
+
+int Renderer::setCamera(const CameraRec* cam) {
+    if (cam) {
+        const float* f = cam->origin;            // 19 consecutive floats
+        static_assert(sizeof(CameraRec) == 19 * sizeof(float), "CameraRec is 19 packed floats");
+        for (int i = 0; i < 19; i++)
+            if (!std::isfinite(f[i])) { last_error = "set_camera: every field must be finite"; return -1; }
+        auto zero = [](const float* v) { return v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f; };
+        if (zero(cam->du) || zero(cam->dv)) { last_error = "set_camera: du and dv must not be zero"; return -1; }
+        if (cam->lens_radius < 0.0f) { last_error = "set_camera: lens_radius must be >= 0"; return -1; }
+        // Rng::make keeps the depth in 9 bits of the seeding word; the lens draws use max_bounces + 3 and + 4
+        if (cam->lens_radius > 0.0f && cfg.max_bounces + 4 > 511) {
+            last_error = "set_camera: a lens needs max_bounces + 4 <= 511 (the seeding word's depth field)";
+            return -1;
+        }
+    }
+    if (allocated) {
+        // The record is rewritten on the caller's stream, which every render call has joined its
+        // pipelines back into: after everything enqueued, before everything to come.  Captured
+        // launches hold the old KParams::camera by value, so the graphs go; a replay in flight
+        // finishes first, as in bindImage.
+        bool graphs = false;
+        for (int i = 0; i < kMaxPipes; i++) graphs = graphs || gexec[i];
+        if (graphs) {
+            PT_HIP(hipStreamSynchronize(stream));
+            for (int i = 1; i < npipes; i++) PT_HIP(hipStreamSynchronize(pstream[i]));
+            dropGraphs();
+        }
+        if (cam) {
+            hipLaunchKernelGGL(k_set_camera, dim3(1), dim3(64), 0, stream, cam_dev, *cam);
+            PT_HIP(hipGetLastError());
+        }
+        kp.camera = cam ? cam_dev : nullptr;
+        for (int i = 0; i < kMaxPipes; i++) pk[i].camera = kp.camera;
+        cache_valid = false;                         // the next render call rebuilds the primary hits
+    }
+    camera_on = cam != nullptr;
+    if (cam) cam_rec = *cam;
+    return allocated ? clearImage() : 0;             // a new view is a new render
+}
+
+int Renderer::camera(CameraRec* out) const {
+    if (out) {
+        if (camera_on) {
+            *out = cam_rec;
+        } else {
+            // the general camera whose rays are the legacy camera's bit for bit (float-representable
+            // cam, plane_x0, plane_y0 and plane_z: the double add of the legacy form is then the float add)
+            *out = CameraRec{};
+            for (int k = 0; k < 3; k++) out->origin[k] = (float)cfg.cam[k];
+            out->p0[0] = (float)cfg.plane_x0; out->p0[1] = (float)cfg.plane_y0; out->p0[2] = (float)cfg.plane_z;
+            out->du[0] = (float)(cfg.plane_w / cfg.width);
+            out->dv[1] = (float)(cfg.plane_h / cfg.height);
+            out->lens_u[0] = 1.0f;
+            out->lens_v[1] = 1.0f;
+        }
+    }
+    return camera_on ? 1 : 0;
+}
+
 int Renderer::setPixelJitter(int on, float width) {
     if (!std::isfinite(width) || width < 0.0f) { last_error = "pixel jitter: width must be finite and >= 0"; return -1; }
     // Rng::make keeps the depth in 9 bits of the seeding word; the draws use max_bounces + 1 and + 2
@@ -3654,6 +3839,8 @@ int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pal
 // unshaded, so the first shade is bounce 1's and the iteration has one more pass,
 // b = 1 .. passes, each the ordinary sort / trace / shade / scan.  n_live (max_bounces + 4
 // entries) holds index passes + 1; k_scan stops counting segments per bounce at 64.
+// With a camera set (k.camera) the generating kernel is k_gen_camera, and `jitter` is also
+// true for an unjittered iteration through a lens.
 int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, const unsigned char* tile_mask, bool jitter) {
     const KParams& k = pk[q];
     const dim3 grid((unsigned)kp.nblocks + 8u);
@@ -3676,7 +3863,8 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, cons
             launchBounce(ku, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
-            if (b == 0 && jitter) launchGenJitter(k, st, iter, tile_mask);
+            if (b == 0 && jitter && k.camera) launchGenCamera(k, st, iter, tile_mask);
+            else if (b == 0 && jitter) launchGenJitter(k, st, iter, tile_mask);
             else if (b == 0 && tile_mask) launchBounceMasked(k, st, grid, iter, tile_mask);
             else launchBounce(k, st, b == 0, grid, iter, b, cfg.accel);
         }
@@ -3734,7 +3922,8 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
     const int passes = cfg.max_bounces > 1 ? cfg.max_bounces : 1;
     // jittered iterations are enqueued directly, like masked ones: never captured, never
     // replayed, so the graphs of the plain loop stay valid across a switch
-    const bool jitter = jitter_on;
+    // ... and so are the iterations through a lens, whose rays are generated too
+    const bool jitter = jitter_on || (camera_on && cam_rec.lens_radius > 0.0f);
     const int np = npipes;
     if (np > 1) {                                   // fork the pipeline streams off the caller's stream
         PT_HIP(hipEventRecord(fork_ev, stream));
@@ -4138,6 +4327,7 @@ void Renderer::freeBuffers() {
     dn_cv[0] = dn_cv[1] = dn_nd = nullptr;
     dn_model = nullptr;
     dn_slope = nullptr;
+    cam_dev = nullptr;
     freeAdaptive();
     allocated = false;
     cache_valid = false;

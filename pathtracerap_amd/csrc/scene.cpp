@@ -414,6 +414,7 @@ int Scene::loadConfig(const std::string& path) {
         const std::string& kw = b[0];
         if (material_from_name(kw) >= 0) continue;
         if (kw == "RENDER") {
+            bool has_eye = false, has_target = false, any_cam = false;
             for (size_t i = 1; i < b.size(); i++) {
                 std::string key = b[i].substr(0, b[i].find(':'));
                 std::string val = b[i].find(':') == std::string::npos ? "" : trim(b[i].substr(b[i].find(':') + 1));
@@ -427,8 +428,23 @@ int Scene::loadConfig(const std::string& path) {
                 } else if (key == "accel") {
                     settings.accel = (val == "bvh") ? ACCEL_BVH : (val == "grid_fast") ? ACCEL_GRID_FAST : ACCEL_GRID;
                     settings.has_accel = true;
+                } else if (key.rfind("camera_", 0) == 0) {
+                    any_cam = true;
+                    const bool vec3 = parse_vec(val, v) && v.size() == 3;
+                    char* end = nullptr;
+                    const double num = std::strtod(val.c_str(), &end);
+                    const bool scalar = !val.empty() && end && *end == 0;
+                    if (key == "camera_eye" && vec3) { for (int k = 0; k < 3; k++) settings.cam_eye[k] = v[k]; has_eye = true; }
+                    else if (key == "camera_target" && vec3) { for (int k = 0; k < 3; k++) settings.cam_target[k] = v[k]; has_target = true; }
+                    else if (key == "camera_up" && vec3) { for (int k = 0; k < 3; k++) settings.cam_up[k] = v[k]; }
+                    else if (key == "camera_fov" && scalar) settings.cam_fov = num;
+                    else if (key == "camera_focus" && scalar && num > 0.0) settings.cam_focus = num;
+                    else if (key == "camera_lens" && scalar) settings.cam_lens = num;
+                    else return fail("bad RENDER line " + b[i]);
                 } else return fail("bad RENDER line " + b[i]);
             }
+            if (any_cam && !(has_eye && has_target)) return fail("RENDER camera needs camera_eye and camera_target");
+            if (any_cam) settings.has_camera = true;
             continue;
         }
         if (kw == "OBJ") {

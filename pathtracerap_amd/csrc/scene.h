@@ -51,6 +51,10 @@ struct RenderSettings {                                 // Config.h constants, r
     int grid[3] = {25, 25, 25};
     int accel = ACCEL_GRID_FAST;
     bool has_width = false, has_iterations = false, has_bounces = false, has_accel = false;
+    // camera_* keys (pt_scene_camera): a look-at view; set when camera_eye and camera_target are given
+    bool has_camera = false;
+    double cam_eye[3] = {0, 0, 0}, cam_target[3] = {0, 0, 0}, cam_up[3] = {0, 1, 0};
+    double cam_fov = 45.0, cam_focus = -1.0, cam_lens = 0.0;    // focus < 0: |target - eye|
 };
 
 class Scene {

@@ -28,7 +28,7 @@ def shard_iterations(total: int, rank: int, world: int) -> tuple[int, int]:
 
 def render_sharded(scene, cfg, total_iters: int, device=None,
                    render_fn: Optional[Callable] = None, moments: bool = False,
-                   jitter: Optional[float] = None):
+                   jitter: Optional[float] = None, camera=None):
     """Render ``total_iters`` samples per pixel across the process group and
     return the summed accumulator (a (W*H*3,) float32 tensor on every rank).
 
@@ -46,6 +46,10 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
     ``jitter``: a width turns on pixel-jittered camera rays (Renderer.set_pixel_jitter)
     on every rank; the offset depends on (iteration, pixel) only, so the shards add up
     to the one-rank render.  None: unjittered.  Ignored with ``render_fn``.
+
+    ``camera``: a ``Camera`` (Renderer.set_camera) every rank renders through; its lens
+    draws depend on (iteration, pixel) only, like the jitter's, so sharding stays exact.
+    None: the config's legacy camera.  Ignored with ``render_fn``.
     """
     import torch
     import torch.distributed as dist
@@ -72,6 +76,8 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
             r.enable_moments(m2.data_ptr(), keepalive=m2)
         if jitter is not None:
             r.set_pixel_jitter(jitter)
+        if camera is not None:
+            r.set_camera(camera)
         r.allocateOnGPU(scene)
         r.renderLoop(first_iter=first, n_iters=n, sync=False)
     if grouped:
