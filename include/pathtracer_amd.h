@@ -480,6 +480,70 @@ int pt_camera_look_at(const double eye[3], const double target[3], const double 
  * (vertical, default 45), camera_focus:D (default |target - eye|), camera_lens:R (default 0).
  * pt_render and the command-line renderer apply it. */
 int pt_scene_camera(const pt_scene *s, int W, int H, pt_camera *out);
+
+/* ---- Environment lighting: an octahedral sky map for the rays that miss (added within ABI 9:
+ * new functions only, pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in
+ * the reference, whose shadeRayKernel gives a missing ray the constant 0.01).  Off by default:
+ * a renderer that never sets an environment computes exactly what it did. ---- */
+typedef struct pt_environment {
+    int n;                        /* the map is n x n texels, 1 <= n <= 2048 */
+    const float *texels_rgb;      /* n*n*3 floats, octahedral layout: texel (row y, column x) at 3*(y*n + x) */
+    float scale[3];               /* multiplies the interpolated texel, per channel */
+    float rotation[9];            /* row-major, world -> environment frame; the frame's +z is the map's centre */
+} pt_environment;
+/* Sets what a ray that leaves the scene brings back, for the iterations enqueued after the
+ * call; env = NULL: back to the constant 0.01.  Only the colour of a ray that has already missed
+ * changes: no trace, no random draw, no slot, no compaction order and no segment count does.
+ * For a missing ray of direction d (not normalised) and colour c, float32 IEEE in exactly this
+ * order, no fused multiply-add; T[y][x] is a texel, |.| clears the sign bit:
+ *   u  = d * (1.0f / sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z))
+ *   e_k = (rotation[3k]*u.x + rotation[3k+1]*u.y) + rotation[3k+2]*u.z          k = 0, 1, 2
+ *   l  = (|e.x| + |e.y|) + |e.z|
+ *   px = e.x / l;  py = e.y / l
+ *   if (e.z < 0) { qx = (1.0f - |py|) * (px >= 0 ? 1.0f : -1.0f);
+ *                  qy = (1.0f - |px|) * (py >= 0 ? 1.0f : -1.0f);  px = qx;  py = qy; }
+ *   per axis p:  f = ((p * 0.5f + 0.5f) * (float)n) - 0.5f;  f = fminf(fmaxf(f, 0.0f), (float)(n - 1))
+ *                i0 = (int)f;  i1 = min(i0 + 1, n - 1);  t = f - (float)i0
+ *   per channel: top = T[y0][x0] + (T[y0][x1] - T[y0][x0]) * tx
+ *                bot = T[y1][x0] + (T[y1][x1] - T[y1][x0]) * tx
+ *                v   = top + (bot - top) * ty
+ *   c = c * (v * scale);  the ray ends (bounces = 0)
+ * The upper hemisphere (e.z >= 0) fills the diamond |px| + |py| <= 1 about the map's centre, the
+ * lower one the four corners.  fmaxf / fminf drop a NaN, so a NaN coordinate (a zero direction)
+ * reads texel (0, 0): no load leaves the map.
+ * Limits.  The lookup is clamp-to-edge bilinear: the map's outer edge is a fold line of the lower
+ * hemisphere, where the interpolation is off by at most half a texel (there is no octahedral
+ * wrap).  The map is sampled by the paths alone (no importance sampling, no shadow rays), so a
+ * small bright sun is noisy.  The image accumulates sqrt(colour) as before.
+ * May be called before or after allocate_on_gpu.  After it the call waits for the renderer's
+ * stream (which every render call has joined its pipelines into), uploads on that stream, drops
+ * the captured graphs when the environment changes between NULL and set, and does what
+ * pt_renderer_clear_image does: a new environment is a new render.  The segment counters and
+ * the primary-hit cache stay.  The texels are copied: the caller's buffer is free after the call.
+ * Refused with a message before anything changes: a null renderer; "set_environment: n must be
+ * 1 .. 2048"; "set_environment: null texels"; "set_environment: every scale entry must be
+ * finite"; "set_environment: every rotation entry must be finite"; "set_environment: every texel
+ * must be finite". */
+int pt_renderer_set_environment(pt_renderer *r, const pt_environment *env);
+/* The current environment: returns 1 when one is set and 0 when none is (< 0: error).  *out (may
+ * be NULL) receives n, scale and rotation, with texels_rgb = NULL; texels_out (may be NULL: ask
+ * for n first) receives the n*n*3 texels. */
+int pt_renderer_environment(pt_renderer *r, pt_environment *out, float *texels_out);
+/* Test hook: the lookup above, without the final c * ..., on the device for `count` directions
+ * dirs[3*count] -> rgb_out[3*count].  Needs allocate_on_gpu and an environment. */
+int pt_renderer_env_lookup(pt_renderer *r, int count, const float *dirs, float *rgb_out);
+/* Fills an n x n octahedral map with a sky (host only): texels_out[3*(y*n + x) + k], k = r, g, b.
+ * Texel (y, x)'s centre is decoded to a direction, float32 in exactly this order:
+ *   px = (((float)x + 0.5f) / (float)n) * 2.0f - 1.0f;  py likewise from y
+ *   ez = (1.0f - |px|) - |py|;  ex = px;  ey = py
+ *   if (ez < 0) { ex = (1.0f - |py|) * (px >= 0 ? 1.0f : -1.0f);
+ *                 ey = (1.0f - |px|) * (py >= 0 ? 1.0f : -1.0f); }
+ *   uz = ez * (1.0f / sqrtf((ex*ex + ey*ey) + ez*ez))
+ *   texel_k = ez >= 0 ? horizon_k + (zenith_k - horizon_k) * uz : ground_k
+ * The environment frame's +z is the zenith; pt_environment's rotation turns it to the world's up.
+ * Refused: a null argument, n outside 1 .. 2048. */
+int pt_environment_sky(const float zenith[3], const float horizon[3], const float ground[3], int n,
+                       float *texels_out);
 void pt_renderer_free(pt_renderer *r);
 
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div

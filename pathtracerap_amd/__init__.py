@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-__all__ = ["Scene", "Renderer", "RenderConfig", "Camera", "look_at", "PathTracerError", "build", "lib", "hw_queues",
+__all__ = ["Scene", "Renderer", "RenderConfig", "Camera", "look_at", "Environment", "PathTracerError", "build", "lib", "hw_queues",
            "MATERIALS", "ACCEL_GRID", "ACCEL_BVH", "ACCEL_GRID_FAST"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -77,6 +77,13 @@ class _Camera(ctypes.Structure):
 
 
 _P_F = ctypes.POINTER(ctypes.c_float)
+
+
+class _Environment(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("texels_rgb", _P_F), ("scale", ctypes.c_float * 3),
+                ("rotation", ctypes.c_float * 9)]
+
+
 _P_I = ctypes.POINTER(ctypes.c_int)
 _P_D = ctypes.POINTER(ctypes.c_double)
 _lib = None
@@ -150,6 +157,10 @@ EXPORTS = [
     ("pt_camera_look_at", ctypes.c_int, [_P_D, _P_D, _P_D, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Camera)]),
     ("pt_scene_camera", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Camera)]),
+    ("pt_renderer_set_environment", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Environment)]),
+    ("pt_renderer_environment", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Environment), _P_F]),
+    ("pt_renderer_env_lookup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F]),
+    ("pt_environment_sky", ctypes.c_int, [_P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
@@ -285,6 +296,103 @@ def look_at(eye, target, up=(0.0, 1.0, 0.0), vfov_deg: float = 45.0, focus_dist:
     _err(lib().pt_camera_look_at(e, t, u, float(vfov_deg), float(focus_dist), float(lens_radius), int(width),
                                  int(height), ctypes.byref(out)), "look_at")
     return Camera.from_c(out)
+
+
+def _up_rotation(up) -> np.ndarray:
+    """The rotation (3, 3), world -> environment frame, whose third row is ``up`` normalised:
+    the environment's +z, the map's centre, points along world ``up``.  With a the axis two
+    after up's largest component, x = normalize(a x z) and y = z x x: (0, 1, 0) gives
+    e = (u.z, u.x, u.y) and (0, 0, 1) the identity.  Computed in double, rounded once."""
+    z = np.asarray(up, np.float64)
+    if z.shape != (3,) or not np.isfinite(z).all() or not z.any():
+        raise ValueError("up must be three finite numbers, not all zero")
+    z = z / np.linalg.norm(z)
+    a = np.zeros(3)
+    a[(int(np.argmax(np.abs(z))) + 2) % 3] = 1.0
+    x = np.cross(a, z)
+    x /= np.linalg.norm(x)
+    return np.stack([x, np.cross(z, x), z]).astype(np.float32)
+
+
+def _octahedral_directions(n: int) -> np.ndarray:
+    """(n, n, 3) float64: the unit direction, in the environment frame, of every texel centre of
+    an n x n octahedral map, row y column x."""
+    p = (np.arange(n) + 0.5) / n * 2.0 - 1.0
+    px, py = np.meshgrid(p, p)                  # px varies along a row
+    ez = 1.0 - np.abs(px) - np.abs(py)
+    low = ez < 0
+    ex = np.where(low, (1.0 - np.abs(py)) * np.where(px >= 0, 1.0, -1.0), px)
+    ey = np.where(low, (1.0 - np.abs(px)) * np.where(py >= 0, 1.0, -1.0), py)
+    d = np.stack([ex, ey, ez], axis=-1)
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+class Environment:
+    """pt_environment (include/pathtracer_amd.h): what a ray that leaves the scene brings back.
+    ``texels``: (n, n, 3) float32 in octahedral layout, 1 <= n <= 2048; ``scale``: per channel;
+    ``rotation``: (3, 3) row-major, world -> environment frame, whose +z is the map's centre."""
+
+    def __init__(self, texels, scale=(1.0, 1.0, 1.0), rotation=None):
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3:
+            raise ValueError("texels must have shape (n, n, 3)")
+        self.texels = t
+        self.scale = np.asarray(scale, np.float32).reshape(3).copy()
+        self.rotation = (np.eye(3, dtype=np.float32) if rotation is None
+                         else np.asarray(rotation, np.float32).reshape(3, 3).copy())
+
+    @property
+    def n(self) -> int:
+        return self.texels.shape[0]
+
+    def c(self) -> _Environment:
+        """The C record; it points into ``self.texels``, so keep ``self`` alive while it is used."""
+        c = _Environment()
+        c.n = self.n
+        c.texels_rgb = _fp(self.texels)
+        for k in range(3):
+            c.scale[k] = float(self.scale[k])
+        for k in range(9):
+            c.rotation[k] = float(self.rotation.reshape(-1)[k])
+        return c
+
+    @classmethod
+    def constant(cls, rgb, scale=(1.0, 1.0, 1.0)) -> "Environment":
+        """One texel: the same radiance from every direction (a number or three)."""
+        return cls(np.broadcast_to(np.asarray(rgb, np.float32), (3,)).reshape(1, 1, 3), scale)
+
+    @classmethod
+    def sky(cls, zenith, horizon, ground=(0.0, 0.0, 0.0), n: int = 64, up=(0.0, 1.0, 0.0)) -> "Environment":
+        """pt_environment_sky: ``horizon`` blended towards ``zenith`` with the height above the
+        horizon, ``ground`` below it; ``up`` is the world direction of the zenith."""
+        z, h, g = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (3,))) for v in (zenith, horizon, ground))
+        t = np.empty((max(int(n), 0), max(int(n), 0), 3), np.float32)
+        _err(lib().pt_environment_sky(_fp(z), _fp(h), _fp(g), int(n), _fp(t)), "environment_sky")
+        return cls(t, rotation=_up_rotation(up))
+
+    @classmethod
+    def from_latlong(cls, image, n: int = 256, up=(0.0, 1.0, 0.0)) -> "Environment":
+        """Resample a latitude-longitude image (rows from +up down to -up, columns once around
+        it; (h, w, 3)) into an n x n octahedral map, on the host in double: every texel centre's
+        direction reads the image bilinearly, wrapping around in longitude and clamped at the
+        poles.  Column 0 starts at the environment frame's +x (see ``_up_rotation``)."""
+        img = np.asarray(image, np.float64)
+        if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise ValueError("image must have shape (h, w, 3)")
+        if not 1 <= int(n) <= 2048:
+            raise ValueError("n must be 1 .. 2048")
+        h, w = img.shape[:2]
+        d = _octahedral_directions(int(n))
+        v = np.clip(np.arccos(np.clip(d[..., 2], -1.0, 1.0)) / np.pi * h - 0.5, 0.0, h - 1.0)
+        u = (np.arctan2(d[..., 1], d[..., 0]) / (2.0 * np.pi) % 1.0) * w - 0.5
+        v0 = np.floor(v).astype(np.int64)
+        u0 = np.floor(u).astype(np.int64)
+        tv, tu = (v - v0)[..., None], (u - u0)[..., None]
+        v1 = np.minimum(v0 + 1, h - 1)
+        u0, u1 = u0 % w, (u0 + 1) % w
+        top = img[v0, u0] + (img[v0, u1] - img[v0, u0]) * tu
+        bot = img[v1, u0] + (img[v1, u1] - img[v1, u0]) * tu
+        return cls((top + (bot - top) * tv).astype(np.float32), rotation=_up_rotation(up))
 
 
 class Scene:
@@ -679,6 +787,29 @@ class Renderer:
         out = _Camera()
         rc = _err(lib().pt_renderer_camera(self._h, ctypes.byref(out)), "camera")
         return bool(rc), Camera.from_c(out)
+
+    def set_environment(self, env: Environment | None) -> None:
+        """What a missing ray brings back (include/pathtracer_amd.h, pt_renderer_set_environment)
+        for the iterations enqueued from now on; None: back to the constant 0.01.  Before or
+        after allocateOnGPU; after it, a new environment starts a new render."""
+        _err(lib().pt_renderer_set_environment(self._h, ctypes.byref(env.c()) if env is not None else None),
+             "set_environment")
+
+    def environment(self) -> Environment | None:
+        """The environment in use (a copy), or None."""
+        c = _Environment()
+        if not _err(lib().pt_renderer_environment(self._h, ctypes.byref(c), None), "environment"):
+            return None
+        t = np.empty((c.n, c.n, 3), np.float32)
+        _err(lib().pt_renderer_environment(self._h, None, _fp(t)), "environment")
+        return Environment(t, tuple(c.scale), np.array(list(c.rotation), np.float32).reshape(3, 3))
+
+    def environment_lookup(self, dirs) -> np.ndarray:
+        """Test hook: the device's lookup (texel times scale) for each of the (n, 3) directions."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.empty_like(d)
+        _err(lib().pt_renderer_env_lookup(self._h, len(d), _fp(d), _fp(out)), "env_lookup")
+        return out
 
     def free(self) -> None:
         if self._h:

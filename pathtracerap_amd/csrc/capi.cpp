@@ -388,6 +388,34 @@ int pt_renderer_camera(pt_renderer* r, pt_camera* out) {
     return rc;
 }
 
+int pt_renderer_set_environment(pt_renderer* r, const pt_environment* env) { R_CALL(r->r->setEnvironment(env)); }
+int pt_renderer_environment(pt_renderer* r, pt_environment* out, float* texels_out) {
+    R_CALL(r->r->environment(out, texels_out));
+}
+int pt_renderer_env_lookup(pt_renderer* r, int count, const float* dirs, float* rgb_out) {
+    R_CALL(r->r->envLookup(count, dirs, rgb_out));
+}
+
+int pt_environment_sky(const float zenith[3], const float horizon[3], const float ground[3], int n, float* texels_out) {
+    if (!zenith || !horizon || !ground || !texels_out) return set_err("environment_sky: null argument");
+    if (n < 1 || n > pt::kEnvMaxN) return set_err("environment_sky: n must be 1 .. 2048");
+    for (int y = 0; y < n; y++)
+        for (int x = 0; x < n; x++) {
+            const float px = (((float)x + 0.5f) / (float)n) * 2.0f - 1.0f;
+            const float py = (((float)y + 0.5f) / (float)n) * 2.0f - 1.0f;
+            const float ez = (1.0f - fabsf(px)) - fabsf(py);
+            float ex = px, ey = py;
+            if (ez < 0.0f) {
+                ex = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f);
+                ey = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
+            }
+            const float uz = pt::normalize(pt::mk3(ex, ey, ez)).z;
+            float* t = texels_out + 3 * ((size_t)y * n + x);
+            for (int k = 0; k < 3; k++) t[k] = ez >= 0.0f ? horizon[k] + (zenith[k] - horizon[k]) * uz : ground[k];
+        }
+    return 0;
+}
+
 int pt_camera_look_at(const double eye[3], const double target[3], const double up[3], double vfov_deg,
                       double focus_dist, double lens_radius, int W, int H, pt_camera* out) {
     if (!eye || !target || !up || !out) return set_err("look_at: null argument");

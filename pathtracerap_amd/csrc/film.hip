@@ -1,7 +1,8 @@
 // film.hip -- per-pixel second moment, noise estimate, render-until-converged, the
 // variance-guided edge-avoiding denoiser, and the host side of tile-masked sampling
 // with its per-tile estimate, mean and adaptive loop (no counterpart in the reference,
-// which renders a fixed ITER samples and writes the raw mean).
+// which renders a fixed ITER samples and writes the raw mean); and the host side of
+// environment lighting with its lookup test hook (pt_env.h), at the end.
 //
 // Every pixel receives one contribution c = sqrt(color) per iteration.  With
 // moments on, every pipeline (a single one too) writes c to its contribution
@@ -856,6 +857,113 @@ int Renderer::renderAdaptive(int first_iter, int min_iters, int max_iters, int c
     if (pixel_samples) *pixel_samples = taken;
     if (mean_err) *mean_err = mean;
     return n_active == 0 ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// Environment lighting (pt_env.h): the host side.  The shading pass reads the record through
+// KParams::env (shade_mat, renderer.hip); nothing else on the device knows of it.
+// ---------------------------------------------------------------------------
+
+// Test hook (pt_renderer_env_lookup): env_radiance of caller-given directions.
+__global__ __launch_bounds__(256) void k_env_lookup(const EnvRec* env, int n, const float* __restrict__ dirs,
+                                                    float* __restrict__ rgb) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const f3 v = env_radiance(*env, mk3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+    rgb[3 * i] = v.x; rgb[3 * i + 1] = v.y; rgb[3 * i + 2] = v.z;
+}
+
+// The texels and the record, on the caller's stream.  The host copies (env_texels, env_rec)
+// stay as they are until the next setEnvironment, which waits for the stream first.
+int Renderer::uploadEnvironment() {
+    const size_t nt = env_texels.size();
+    if (nt > env_texels_cap) {
+        if (env_texels_dev) PT_HIP(hipFree(env_texels_dev));
+        env_texels_dev = nullptr;
+        env_texels_cap = 0;
+        PT_HIP(hipMalloc(&env_texels_dev, nt * sizeof(float4)));
+        env_texels_cap = nt;
+    }
+    PT_HIP(hipMemcpyAsync(env_texels_dev, env_texels.data(), nt * sizeof(float4), hipMemcpyHostToDevice, stream));
+    env_rec.texels = env_texels_dev;
+    PT_HIP(hipMemcpyAsync(env_dev, &env_rec, sizeof(EnvRec), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+int Renderer::setEnvironment(const pt_environment* env) {
+    if (env) {
+        if (env->n < 1 || env->n > kEnvMaxN) { last_error = "set_environment: n must be 1 .. 2048"; return -1; }
+        if (!env->texels_rgb) { last_error = "set_environment: null texels"; return -1; }
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(env->scale[k])) { last_error = "set_environment: every scale entry must be finite"; return -1; }
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(env->rotation[k])) { last_error = "set_environment: every rotation entry must be finite"; return -1; }
+        const size_t nf = (size_t)env->n * env->n * 3;
+        for (size_t i = 0; i < nf; i++)
+            if (!std::isfinite(env->texels_rgb[i])) { last_error = "set_environment: every texel must be finite"; return -1; }
+    }
+    if (allocated) {
+        // Every render call has joined its pipelines back into the caller's stream; once that
+        // stream is idle nothing reads the old texels or the host copies.  Captured launches
+        // hold KParams::env by value, so the graphs go when it changes between null and set.
+        PT_HIP(hipStreamSynchronize(stream));
+        if ((env != nullptr) != env_on) {
+            for (int i = 1; i < npipes; i++) PT_HIP(hipStreamSynchronize(pstream[i]));
+            dropGraphs();
+        }
+    }
+    env_on = env != nullptr;
+    if (env) {
+        const size_t nt = (size_t)env->n * env->n;
+        env_texels.resize(nt);
+        for (size_t i = 0; i < nt; i++)
+            env_texels[i] = make_float4(env->texels_rgb[3 * i], env->texels_rgb[3 * i + 1], env->texels_rgb[3 * i + 2], 0.0f);
+        env_rec.n = env->n;
+        for (int k = 0; k < 3; k++) env_rec.scale[k] = env->scale[k];
+        for (int k = 0; k < 9; k++) env_rec.rot[k] = env->rotation[k];
+    }
+    if (!allocated) return 0;
+    if (env && uploadEnvironment() != 0) return -1;
+    kp.env = env ? env_dev : nullptr;
+    for (int i = 0; i < kMaxPipes; i++) pk[i].env = kp.env;
+    return clearImage();                             // a new environment is a new render; the primary hits stay
+}
+
+int Renderer::environment(pt_environment* out, float* texels_out) const {
+    if (!env_on) return 0;
+    if (out) {
+        out->n = env_rec.n;
+        out->texels_rgb = nullptr;
+        for (int k = 0; k < 3; k++) out->scale[k] = env_rec.scale[k];
+        for (int k = 0; k < 9; k++) out->rotation[k] = env_rec.rot[k];
+    }
+    if (texels_out)
+        for (size_t i = 0; i < env_texels.size(); i++) {
+            texels_out[3 * i] = env_texels[i].x; texels_out[3 * i + 1] = env_texels[i].y; texels_out[3 * i + 2] = env_texels[i].z;
+        }
+    return 1;
+}
+
+int Renderer::envLookup(int count, const float* dirs, float* rgb_out) {
+    if (!allocated) { last_error = "env_lookup: not allocated"; return -1; }
+    if (!env_on) { last_error = "env_lookup: no environment is set"; return -1; }
+    if (count < 0 || (count > 0 && (!dirs || !rgb_out))) { last_error = "env_lookup: bad arguments"; return -1; }
+    if (count == 0) return 0;
+    float *d_d = nullptr, *d_c = nullptr;
+    const size_t bytes = (size_t)count * 3 * sizeof(float);
+    PT_HIP(hipMalloc(&d_d, bytes));
+    hipError_t e = hipMalloc(&d_c, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d, dirs, bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_env_lookup, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, env_dev, count, d_d, d_c);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_c, bytes, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    hipFree(d_d);
+    hipFree(d_c);
+    if (e != hipSuccess) return fail(e, "env_lookup");
+    return 0;
 }
 
 }  // namespace pt

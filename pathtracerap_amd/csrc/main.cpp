@@ -5,6 +5,12 @@
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
 //                  [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
 //                  [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] [--focus D] [--lens R]]
+//                  [--sky ZR ZG ZB HR HG HB [--ground R G B]]
+//
+// --sky: environment lighting (pt_environment_sky, pt_renderer_set_environment): a ray that
+// leaves the scene brings back the horizon colour blended towards the zenith colour with its
+// height, and --ground (default 0 0 0) from below the horizon; world +y is up.  A 64 x 64
+// octahedral map.  Without it such a ray brings back the reference's constant 0.01.
 //
 // --look-from / --look-at: a free camera (pt_camera_look_at, pt_renderer_set_camera) at the
 // first point looking at the second, with --up (default 0 1 0), a vertical field of view of
@@ -48,7 +54,7 @@ int main(int argc, char** argv) {
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
                              "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]] "
                              "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
-                             "[--focus D] [--lens R]]\n", argv[0]);
+                             "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -68,6 +74,8 @@ int main(int argc, char** argv) {
     double eye[3] = {0, 0, 0}, target[3] = {0, 0, 0}, up[3] = {0, 1, 0};
     double fov = 45.0, focus = 0.0, lens = 0.0;       // no --focus: the distance from eye to target
     auto vec3 = [&](double* v, int& i) { for (int k = 0; k < 3; k++) v[k] = std::atof(argv[++i]); };
+    bool sky = false, has_ground = false;
+    double zenith[3] = {0, 0, 0}, horizon[3] = {0, 0, 0}, ground[3] = {0, 0, 0};
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
     for (int i = 2; i < argc; i++) {
@@ -89,6 +97,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--fov") && i + 1 < argc) { fov = std::atof(argv[++i]); cam_opt = true; }
         else if (!std::strcmp(argv[i], "--focus") && i + 1 < argc) { focus = std::atof(argv[++i]); has_focus = cam_opt = true; }
         else if (!std::strcmp(argv[i], "--lens") && i + 1 < argc) { lens = std::atof(argv[++i]); cam_opt = true; }
+        else if (!std::strcmp(argv[i], "--sky") && i + 6 < argc) { vec3(zenith, i); vec3(horizon, i); sky = true; }
+        else if (!std::strcmp(argv[i], "--ground") && i + 3 < argc) { vec3(ground, i); has_ground = true; }
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
@@ -99,6 +109,10 @@ int main(int argc, char** argv) {
     }
     if (has_from != has_at || (cam_opt && !has_from)) {
         std::fprintf(stderr, "a camera needs both --look-from and --look-at\n");
+        return 2;
+    }
+    if (has_ground && !sky) {
+        std::fprintf(stderr, "--ground needs --sky\n");
         return 2;
     }
     pt_camera cam;
@@ -121,6 +135,18 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (has_cam > 0 && pt_renderer_set_camera(r, &cam) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+    if (sky) {
+        constexpr int n = 64;
+        static float texels[n * n * 3];
+        float z[3], h[3], g[3];
+        for (int k = 0; k < 3; k++) { z[k] = (float)zenith[k]; h[k] = (float)horizon[k]; g[k] = (float)ground[k]; }
+        // the environment frame's +z (the zenith) is world +y: e = (u.z, u.x, u.y)
+        pt_environment env = {n, texels, {1.0f, 1.0f, 1.0f}, {0, 0, 1, 1, 0, 0, 0, 1, 0}};
+        if (pt_environment_sky(z, h, g, n, texels) < 0 || pt_renderer_set_environment(r, &env) < 0) {
+            std::fprintf(stderr, "%s\n", pt_last_error());
+            return 1;
+        }
+    }
     if (jitter && pt_renderer_set_pixel_jitter(r, 1, jitter_width) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     int iters = cfg.iterations;
     auto t0 = std::chrono::high_resolution_clock::now();

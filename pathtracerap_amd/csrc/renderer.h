@@ -14,7 +14,10 @@
 #include <string>
 #include <vector>
 
+#include "pt_env.h"
 #include "scene.h"
+
+struct pt_environment;           // include/pathtracer_amd.h
 
 namespace pt {
 
@@ -121,6 +124,8 @@ struct KParams {
                                         // fields the trace kernels read, so those keep their argument offsets
     const CameraRec* camera;            // setCamera: the free camera camera_ray and k_gen_camera read; null: the
                                         // config's legacy camera (cam_*, plane_*, step_*).  Last, for the same reason
+    const EnvRec* env;                  // setEnvironment: the map shade_mat reads for a ray that misses; null: the
+                                        // reference's constant 0.01.  Last, for the same reason
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
@@ -208,6 +213,13 @@ public:
     // 1.  Before or after allocateOnGPU; after it, a new view starts a new render
     int setCamera(const CameraRec* cam);
     int camera(CameraRec* out) const;                // 1: a camera is set; 0: legacy (out = its equivalent)
+    // Environment lighting (film.hip, pt_env.h; no counterpart in the reference): the colour of a ray
+    // that misses, from an octahedral map of n * n RGB texels.  Null = the constant 0.01.  Before or
+    // after allocateOnGPU; after it, a new environment starts a new render (the primary hits stay)
+    int setEnvironment(const pt_environment* env);
+    // 1: set, 0: none.  out: n, scale and rotation (texels_rgb null); texels_out: n * n * 3 floats
+    int environment(pt_environment* out, float* texels_out) const;
+    int envLookup(int count, const float* dirs, float* rgb_out);     // test hook: env_radiance of each direction
 
     RenderConfig cfg;
     std::string last_error;
@@ -278,6 +290,13 @@ private:
     bool camera_on = false;              // setCamera: cam_rec holds the view; kp.camera / pk[].camera point at cam_dev
     CameraRec cam_rec{};
     CameraRec* cam_dev = nullptr;        // the device record (allocateOnGPU)
+    bool env_on = false;                 // setEnvironment: kp.env / pk[].env point at env_dev
+    EnvRec env_rec{};                    // n, scale, rot (texels: env_texels_dev once allocated)
+    std::vector<float4> env_texels;      // the host copy, one float4 per texel
+    EnvRec* env_dev = nullptr;           // the device record (allocateOnGPU)
+    float4* env_texels_dev = nullptr;    // the device texels and how many fit
+    size_t env_texels_cap = 0;
+    int uploadEnvironment();
     bool slot_map = true;                // k_sort_scatter writes KParams::slot_src for the shading pass (PT_SLOT_MAP)
     bool jitter_sort1 = false;           // ray sort before a jittered iteration's bounce-1 trace too (PT_JITTER_SORT=1)
     int* tile_counts_dev = nullptr;      // adaptiveNoise / adaptiveMean: the counts, uploaded per call

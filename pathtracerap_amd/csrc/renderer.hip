@@ -1196,7 +1196,8 @@ struct RayState { f3 o, d, c; int pixel, bounces; };
 // shadeRayKernel (Renderer.cpp:411-479) for one ray; slot = iray.
 // mt, mc: the hit model's material type and colour, read only for a hit of a ray with
 // bounces left (shade() loads them then; the hit-buffer pass has them loaded already).
-__device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, int slot, int mt, f3 mc) {
+// env: KParams::env (a kernel argument: wave-uniform); its record is read only by a ray that misses.
+__device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, int slot, int mt, f3 mc, const EnvRec* env) {
     if (r.bounces <= 0) r.c = r.c * mk3(0.01f, 0.01f, 0.01f);
     if (h.dist < kFMax) {
         const f3 dir = normalize(r.d);
@@ -1222,7 +1223,7 @@ __device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, i
         }
     } else {
         r.bounces = 0;
-        r.c = r.c * mk3(0.01f, 0.01f, 0.01f);
+        r.c = r.c * (env ? env_radiance(*env, r.d) : mk3(0.01f, 0.01f, 0.01f));
         return;
     }
     r.bounces--;
@@ -1236,7 +1237,7 @@ __device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& 
         mt = S.mat_type;
         mc = mk3(S.color[0], S.color[1], S.color[2]);
     }
-    shade_mat(r, h, iter, slot, mt, mc);
+    shade_mat(r, h, iter, slot, mt, mc, p.env);
 }
 
 // ---------------------------------------------------------------------------
@@ -2639,7 +2640,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             h.dist = hh.x;
             h.model = hm;
             h.n = hm >= 0 ? hn : mk3(0, 0, 0);
-            shade_mat(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc);
+            shade_mat(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc, p.env);
         }
     } else if (active) {
         if (FIRST) {
@@ -3370,6 +3371,10 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     // the free camera's record (setCamera); kernels see it only while a camera is set
     PT_HIP(upload(allocs, &cam_dev, &cam_rec, sizeof(CameraRec), stream));
     kp.camera = camera_on ? cam_dev : nullptr;
+    // the environment's record and texels (setEnvironment), likewise
+    PT_HIP(upload(allocs, &env_dev, nullptr, sizeof(EnvRec), stream));
+    if (env_on && uploadEnvironment() != 0) return -1;
+    kp.env = env_on ? env_dev : nullptr;
     if (external_image) kp.image = ext_image;
     else PT_HIP(upload(allocs, &kp.image, nullptr, (size_t)npix_all * 3 * sizeof(float), stream));
     {
@@ -4328,6 +4333,10 @@ void Renderer::freeBuffers() {
     dn_model = nullptr;
     dn_slope = nullptr;
     cam_dev = nullptr;
+    env_dev = nullptr;
+    if (env_texels_dev) hipFree(env_texels_dev);     // not in allocs: setEnvironment may replace it
+    env_texels_dev = nullptr;
+    env_texels_cap = 0;
     freeAdaptive();
     allocated = false;
     cache_valid = false;

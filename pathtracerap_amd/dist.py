@@ -28,7 +28,7 @@ def shard_iterations(total: int, rank: int, world: int) -> tuple[int, int]:
 
 def render_sharded(scene, cfg, total_iters: int, device=None,
                    render_fn: Optional[Callable] = None, moments: bool = False,
-                   jitter: Optional[float] = None, camera=None):
+                   jitter: Optional[float] = None, camera=None, environment=None):
     """Render ``total_iters`` samples per pixel across the process group and
     return the summed accumulator (a (W*H*3,) float32 tensor on every rank).
 
@@ -50,6 +50,10 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
     ``camera``: a ``Camera`` (Renderer.set_camera) every rank renders through; its lens
     draws depend on (iteration, pixel) only, like the jitter's, so sharding stays exact.
     None: the config's legacy camera.  Ignored with ``render_fn``.
+
+    ``environment``: an ``Environment`` (Renderer.set_environment) every rank lights its
+    missing rays with; the lookup depends on the ray only, so the shards add up.  None: the
+    constant 0.01.  Ignored with ``render_fn``.
     """
     import torch
     import torch.distributed as dist
@@ -78,6 +82,8 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
             r.set_pixel_jitter(jitter)
         if camera is not None:
             r.set_camera(camera)
+        if environment is not None:
+            r.set_environment(environment)
         r.allocateOnGPU(scene)
         r.renderLoop(first_iter=first, n_iters=n, sync=False)
     if grouped:
