@@ -94,6 +94,55 @@ int pt_scene_add_mesh(pt_scene *s, const float *pos, const float *nrm, int nv,
                       const int *tris, int nt);                        /* -> mesh index */
 int pt_scene_add_model(pt_scene *s, int mesh, const float scale[3], const float rot_deg[3],
                        const float translate[3], int material, const float color[3]); /* -> model index */
+/* ---- Smooth shading: the hit normal interpolates the vertex normals, per model (added within
+ * ABI 9: new functions only; pt_scene_add_model, pt_render_config and PT_ABI_VERSION are
+ * unchanged.  No counterpart in the reference, whose Renderer.cpp:203 averages a triangle's three
+ * vertex normals into one, so every curved mesh renders as facets).  Off by default: a scene with
+ * no smooth model allocates, launches and computes exactly what it did. ----
+ * Sets (on != 0) or clears the flag of one model; model = -1: of every model added so far.  May be
+ * called any time after the model exists, before or after pt_scene_build: the grid and the BLAS are
+ * not touched.  pt_renderer_allocate_on_gpu snapshots the flags: a change made afterwards applies
+ * to the next allocation.  When some model is smooth, the allocation also uploads a shading table
+ * of 96 bytes per scene triangle (v0, e1, e2, n0, n1, n2), shared by all pipelines.  Refused:
+ * "setModelSmooth: bad model index".
+ * A hit on a smooth model uses the normal n below wherever the flat normal was used: the scatter
+ * direction, the mirror reflection and the origin offset ip + n*0.1f of the shading; the
+ * primary-hit cache, and hence pt_renderer_primary_hits and the denoiser's guides; and the normals
+ * pt_renderer_intersect_rays and pt_renderer_trace_rays report.
+ * Inputs: the world-space ray (o, d), d not normalised; the world distance dist; the hit model M
+ * with its world_to_model w2m (rows 0..2) and nm = inverse(mat3(model_to_world)); the scene
+ * triangle's v0, e1 = v1 - v0, e2 = v2 - v0 (model space, as the triangle test reads them) and its
+ * stored vertex normals n0, n1, n2 (vnrm of pt_scene_export, the x1000 values); g, the flat unit
+ * world normal normalize(nm * normalize((n0 + n1 + n2) * (1/3))).  float32 IEEE in exactly this
+ * order, no fused multiply-add; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, normalize(a) =
+ * a * (1.0f / sqrtf(dot(a, a))), (w2m * p)_k = (w2m[0][k]*p.x + w2m[1][k]*p.y) + (w2m[2][k]*p.z +
+ * w2m[3][k]*1.0f), (nm * m)_r = (nm[r][0]*m.x + nm[r][1]*m.y) + nm[r][2]*m.z:
+ *   dir = normalize(d);  ip = o + dir * dist                  (the shading's own hit point)
+ *   pm  = w2m * ip;  q = pm - v0
+ *   d11 = dot(e1,e1); d12 = dot(e1,e2); d22 = dot(e2,e2); q1 = dot(q,e1); q2 = dot(q,e2)
+ *   den = d11*d22 - d12*d12
+ *   b1 = (d22*q1 - d12*q2) / den;   b2 = (d11*q2 - d12*q1) / den
+ *   b1 = fminf(fmaxf(b1, 0.0f), 1.0f);  b2 = fminf(fmaxf(b2, 0.0f), 1.0f - b1);  b0 = (1.0f - b1) - b2
+ *   m  = (n0*b0 + n1*b1) + n2*b2                               (per component)
+ *   s  = normalize(nm * m)
+ *   n  = (s.x, s.y, s.z all finite and dot(s, g) > 0) ? s : g
+ * fmaxf / fminf drop a NaN, so a zero-area triangle (den = 0) lands on n0 or a corner without a
+ * special case.  The triangle test accepts points a tolerance outside the triangle; the clamp
+ * keeps those on its edge.  n is a function of (o, d, dist, model, triangle) alone: every path
+ * that shades a hit computes the same bits.
+ * Limits.  A scattered or reflected direction may point below the geometric surface (the usual
+ * shading-normal terminator); nothing is done about it.  g is itself the average of the vertex
+ * normals, so dot(s, g) <= 0 catches a vertex normal that opposes its neighbours, which falls back
+ * to the flat normal, not a mesh whose normals all oppose the winding: there g opposes it too and
+ * smooth shading follows the normals, as flat shading does.  Normals that interpolate to zero
+ * (s not finite) fall back to the flat normal as well.  An OBJ file without
+ * `vn` gets per-corner geometric normals from the loader, so smooth equals flat there up to
+ * rounding: welded normals are not generated.
+ * Config grammar: the optional attribute shading:smooth or shading:flat on MESH, SPHERE and BOX
+ * blocks (another value is refused: "bad attribute ..."). */
+int pt_scene_set_model_smooth(pt_scene *s, int model, int on);
+/* The flag of one model: 0 or 1; negative: error ("pt_scene_model_smooth: bad model index"). */
+int pt_scene_model_smooth(const pt_scene *s, int model);
 /* with_bvh: also build the per-mesh BLAS (needed by PT_ACCEL_GRID_FAST and PT_ACCEL_BVH;
  * pt_renderer_allocate_on_gpu adds it on demand to a scene built without it). */
 int pt_scene_build(pt_scene *s, const int grid[3], int with_bvh);

@@ -102,6 +102,8 @@ EXPORTS = [
     ("pt_scene_load_obj", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     ("pt_scene_add_mesh", ctypes.c_int, [ctypes.c_void_p, _P_F, _P_F, ctypes.c_int, _P_I, ctypes.c_int]),
     ("pt_scene_add_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
+    ("pt_scene_set_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    ("pt_scene_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("pt_scene_build", ctypes.c_int, [ctypes.c_void_p, _P_I, ctypes.c_int]),
     ("pt_scene_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
     ("pt_scene_export", ctypes.c_int, [ctypes.c_void_p, _P_F, _P_F, _P_I, _P_I, _P_F, _P_I, _P_F, _P_F,
@@ -436,11 +438,26 @@ class Scene:
         tris = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
         return _err(lib().pt_scene_add_mesh(self._h, _fp(pos), _fp(nrm), len(pos), _ip(tris), len(tris)), "addMesh")
 
-    def addModel(self, mesh: int, scale, rot_deg, translate, material, color) -> int:
+    def addModel(self, mesh: int, scale, rot_deg, translate, material, color, smooth: bool = False) -> int:
         mt = MATERIALS[material] if isinstance(material, str) else int(material)
         s = np.array(scale, np.float32); r = np.array(rot_deg, np.float32)
         t = np.array(translate, np.float32); c = np.array(color, np.float32)
-        return _err(lib().pt_scene_add_model(self._h, int(mesh), _fp(s), _fp(r), _fp(t), mt, _fp(c)), "addModel")
+        m = _err(lib().pt_scene_add_model(self._h, int(mesh), _fp(s), _fp(r), _fp(t), mt, _fp(c)), "addModel")
+        if smooth:
+            self.set_smooth(m)
+        return m
+
+    def set_smooth(self, model: int | None = None, on: bool = True) -> None:
+        """Shade ``model`` (None: every model added so far) with the interpolated vertex normals
+        instead of one normal per triangle (pt_scene_set_model_smooth).  Any time after the model
+        exists, before or after ``build``; a renderer reads the flags in ``allocateOnGPU``."""
+        _err(lib().pt_scene_set_model_smooth(self._h, -1 if model is None else int(model), 1 if on else 0),
+             "set_smooth")
+
+    def smooth(self) -> np.ndarray:
+        """The smooth flag of every model, a bool array (pt_scene_model_smooth)."""
+        n = self.counts()["nmodel"]
+        return np.array([_err(lib().pt_scene_model_smooth(self._h, i), "smooth") != 0 for i in range(n)], bool)
 
     def build(self, grid=(25, 25, 25), bvh: bool = True) -> None:
         """addMeshesToGrid (grid) + the per-mesh BLAS that ACCEL_GRID_FAST / ACCEL_BVH

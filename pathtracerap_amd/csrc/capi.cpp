@@ -121,6 +121,14 @@ int pt_scene_add_model(pt_scene* s, int mesh, const float scale[3], const float 
     SCENE_CALL(s->s.addModel(mesh, scale, rot, tr, material, color));
 }
 
+int pt_scene_set_model_smooth(pt_scene* s, int model, int on) { SCENE_CALL(s->s.setModelSmooth(model, on != 0)); }
+
+int pt_scene_model_smooth(const pt_scene* s, int model) {
+    if (!s) return set_err("null scene");
+    const int rc = s->s.modelSmooth(model);
+    return rc < 0 ? set_err("pt_scene_model_smooth: bad model index") : rc;
+}
+
 int pt_scene_build(pt_scene* s, const int grid[3], int with_bvh) {
     const int def[3] = {25, 25, 25};
     SCENE_CALL(s->s.build(grid ? grid : def, with_bvh != 0));

@@ -5,7 +5,11 @@
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
 //                  [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
 //                  [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] [--focus D] [--lens R]]
-//                  [--sky ZR ZG ZB HR HG HB [--ground R G B]]
+//                  [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]
+//
+// --smooth: smooth shading for every model (pt_scene_set_model_smooth with model -1): a hit's
+// normal interpolates the vertex normals instead of using one per triangle.  Without it the
+// scene file's shading:smooth attributes apply.
 //
 // --sky: environment lighting (pt_environment_sky, pt_renderer_set_environment): a ray that
 // leaves the scene brings back the horizon colour blended towards the zenith colour with its
@@ -54,7 +58,7 @@ int main(int argc, char** argv) {
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
                              "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]] "
                              "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
-                             "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]]\n", argv[0]);
+                             "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -74,7 +78,7 @@ int main(int argc, char** argv) {
     double eye[3] = {0, 0, 0}, target[3] = {0, 0, 0}, up[3] = {0, 1, 0};
     double fov = 45.0, focus = 0.0, lens = 0.0;       // no --focus: the distance from eye to target
     auto vec3 = [&](double* v, int& i) { for (int k = 0; k < 3; k++) v[k] = std::atof(argv[++i]); };
-    bool sky = false, has_ground = false;
+    bool sky = false, has_ground = false, smooth = false;
     double zenith[3] = {0, 0, 0}, horizon[3] = {0, 0, 0}, ground[3] = {0, 0, 0};
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
@@ -99,6 +103,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lens") && i + 1 < argc) { lens = std::atof(argv[++i]); cam_opt = true; }
         else if (!std::strcmp(argv[i], "--sky") && i + 6 < argc) { vec3(zenith, i); vec3(horizon, i); sky = true; }
         else if (!std::strcmp(argv[i], "--ground") && i + 3 < argc) { vec3(ground, i); has_ground = true; }
+        else if (!std::strcmp(argv[i], "--smooth")) smooth = true;
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
@@ -128,6 +133,7 @@ int main(int argc, char** argv) {
         has_cam = pt_scene_camera(s, cfg.width, cfg.height, &cam);
     }
     if (has_cam < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+    if (smooth && pt_scene_set_model_smooth(s, -1, 1) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
     if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {

@@ -52,11 +52,24 @@ struct ModelRec {
 };
 static_assert(sizeof(ModelRec) == 62 * 4, "ModelRec layout");
 
-// The instance's material (Primitive.h:68-84), read by the shading pass.
+// The instance's material (Primitive.h:68-84), read by the shading pass, and its smooth-shading
+// flag (read only when the renderer holds a shading table, KParams::smooth).  32 bytes: the
+// record's address stays a shift of the model index.
 struct ModelShade {
     float color[3];       // Material::color
     int mat_type;         // Material::MaterialType
+    int smooth;           // 1: the hit normal interpolates the vertex normals (pt_scene_set_model_smooth)
+    int pad[3];
 };
+static_assert(sizeof(ModelShade) == 32, "ModelShade layout");
+
+// One triangle of the shading table (KParams::smooth): what the smooth hit normal reads, one
+// 96-byte record -- tri_geom's v0, e1, e2 and the three stored vertex normals (w lanes unused).
+struct TriShade {
+    float v0[4], e1[4], e2[4];
+    float n0[4], n1[4], n2[4];
+};
+static_assert(sizeof(TriShade) == 96, "TriShade layout");
 
 // 2-wide BVH node: both children's boxes in one 64-byte line.
 // link/count: count == 0 -> link is a child node index; count > 0 -> link is

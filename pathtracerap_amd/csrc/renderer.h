@@ -126,6 +126,9 @@ struct KParams {
                                         // config's legacy camera (cam_*, plane_*, step_*).  Last, for the same reason
     const EnvRec* env;                  // setEnvironment: the map shade_mat reads for a ray that misses; null: the
                                         // reference's constant 0.01.  Last, for the same reason
+    const TriShade* smooth;             // the shading table (one record per scene triangle) of a scene with a
+                                        // smooth model; null: every hit normal is the flat one and nothing
+                                        // more is loaded.  Static per allocation.  Last, for the same reason
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)

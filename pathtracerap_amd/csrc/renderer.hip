@@ -1111,6 +1111,50 @@ __device__ __forceinline__ Hit make_hit(const KParams& p, float gdist, int gmode
     return h;
 }
 
+// The smooth hit normal (include/pathtracer_amd.h, pt_scene_set_model_smooth, states it): the
+// barycentric interpolation of the triangle's stored vertex normals at the hit point, clamped
+// onto the triangle, in place of the flat normal g; float32 in the header's order.  o, d: the
+// world ray (d not normalised); dist: the world distance; w2m, nm: the hit model's records;
+// T: the triangle's shading-table record.  A function of these alone, so every path that
+// shades a hit gets the same bits.
+struct TriShadeRec { float4 v0, e1, e2, n0, n1, n2; };
+__device__ __forceinline__ TriShadeRec load_tri_shade(const TriShade* tab, int tri) {
+    const float4* q = reinterpret_cast<const float4*>(tab + tri);
+    TriShadeRec T;
+    T.v0 = q[0]; T.e1 = q[1]; T.e2 = q[2]; T.n0 = q[3]; T.n1 = q[4]; T.n2 = q[5];
+    return T;
+}
+__device__ __forceinline__ f3 smooth_normal(const float* w2m, const float* nm, const TriShadeRec& T, f3 o, f3 d,
+                                            float dist, f3 g) {
+    const f3 dir = normalize(d);
+    const f3 ip = o + dir * dist;
+    const f3 pm = xform12(w2m, ip, 1.0f);
+    const f3 e1 = mk3(T.e1.x, T.e1.y, T.e1.z), e2 = mk3(T.e2.x, T.e2.y, T.e2.z);
+    const f3 q = pm - mk3(T.v0.x, T.v0.y, T.v0.z);
+    const float d11 = dot(e1, e1), d12 = dot(e1, e2), d22 = dot(e2, e2), q1 = dot(q, e1), q2 = dot(q, e2);
+    const float den = d11 * d22 - d12 * d12;
+    float b1 = (d22 * q1 - d12 * q2) / den;
+    float b2 = (d11 * q2 - d12 * q1) / den;
+    b1 = fminf(fmaxf(b1, 0.0f), 1.0f);              // fmaxf / fminf drop a NaN (den = 0)
+    b2 = fminf(fmaxf(b2, 0.0f), 1.0f - b1);
+    const float b0 = (1.0f - b1) - b2;
+    const f3 m = mk3((T.n0.x * b0 + T.n1.x * b1) + T.n2.x * b2, (T.n0.y * b0 + T.n1.y * b1) + T.n2.y * b2,
+                     (T.n0.z * b0 + T.n1.z * b1) + T.n2.z * b2);
+    const f3 s = normalize(xform_normal9(nm, m));
+    const float inf = __builtin_inff();
+    const bool ok = (absr(s.x) < inf) & (absr(s.y) < inf) & (absr(s.z) < inf) & (dot(s, g) > 0.0f);
+    return ok ? s : g;
+}
+// The hit normal the shading pass uses: g, or smooth_normal on a smooth model.  p.smooth is a
+// kernel argument (wave-uniform): a scene without a smooth model loads nothing here.  The
+// slot-map form of k_bounce<rest, hitbuf, BS, true> restates this selection (model >= 0,
+// tri >= 0, the model's flag) with its loads hoisted: an edit here belongs there too.
+__device__ __forceinline__ f3 shading_normal(const KParams& p, f3 o, f3 d, float dist, int model, int tri, f3 g) {
+    if (!p.smooth || model < 0 || tri < 0 || !p.shade[model].smooth) return g;
+    const ModelRec& M = p.models[model];
+    return smooth_normal(M.w2m, M.nm, load_tri_shade(p.smooth, tri), o, d, dist, g);
+}
+
 // Hit record of the split trace -> shade path (p.hit4 / p.hitm, slot j):
 // (dist, triangle) + model.  The shading pass fetches the triangle normal and
 // transforms it with make_hit's float operations (the same values): the
@@ -1131,6 +1175,12 @@ __device__ __forceinline__ Hit get_hit(const KParams& p, int hj) {
         const float4 tn = tri >= 0 ? p.tri_normal[tri] : make_float4(0, 0, 0, 0);
         h.n = normalize(xform_normal9(p.models[h.model].nm, mk3(tn.x, tn.y, tn.z)));
     }
+    return h;
+}
+// get_hit for the slot's ray (o, d): the normal is the shading normal.
+__device__ __forceinline__ Hit get_hit(const KParams& p, int hj, f3 o, f3 d) {
+    Hit h = get_hit(p, hj);
+    if (p.smooth) h.n = shading_normal(p, o, d, h.dist, h.model, __float_as_int(p.hit4[hj].y), h.n);
     return h;
 }
 
@@ -1165,7 +1215,9 @@ __device__ Hit intersect_scene(const KParams& p, f3 orig, f3 dir, int* stack, in
     float gdist;
     int gmodel, gtri;
     intersect_scene_g<ACCEL, STRIDE>(p, orig, dir, stack, hs, gdist, gmodel, gtri);
-    return make_hit(p, gdist, gmodel, gtri);
+    Hit h = make_hit(p, gdist, gmodel, gtri);
+    if (p.smooth) h.n = shading_normal(p, orig, dir, h.dist, h.model, gtri, h.n);
+    return h;
 }
 
 // The free camera's point of pixel coordinates (fx, fy): (p0 + fx*du) + fy*dv per coordinate,
@@ -2589,7 +2641,10 @@ __device__ __forceinline__ void put_sort_key(const KParams& p, int dst, f3 o, f3
 }
 
 // One bounce for every live ray: gather -> intersect -> shade -> compact / accumulate.
-template <bool FIRST, int ACCEL, int BS>
+// SMOOTH: the hit-buffer pass of a scene with a smooth model (KParams::smooth set), its own
+// instantiation picked at launch, so the pass of every other scene keeps the registers it
+// had (42 VGPRs against 64); the other forms test the pointer where they compute a normal.
+template <bool FIRST, int ACCEL, int BS, bool SMOOTH = false>
 __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_MINWAVES) void k_bounce(KParams p, int iter, int bounce) {
     __shared__ int s_stack[(!FIRST && ACCEL != ACCEL_GRID && ACCEL != kAccelHitBuffer) ? kStack * BS : 1];
     __shared__ int4 s_hs[(!FIRST && ACCEL == ACCEL_GRID_FAST) ? kHitCap * BS : 1];
@@ -2636,7 +2691,18 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             const int mt = S.mat_type;
             const f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
             const float4 tn = tri >= 0 ? tnl : make_float4(0, 0, 0, 0);
-            const f3 hn = normalize(xform_normal9(nm, mk3(tn.x, tn.y, tn.z)));
+            f3 hn = normalize(xform_normal9(nm, mk3(tn.x, tn.y, tn.z)));
+            if (SMOOTH) {
+                // shading_normal's values (keep the two in step); the table record, the model's world_to_model and
+                // its flag are loaded unconditionally, in the round trip of the loads above
+                const TriShadeRec T = load_tri_shade(p.smooth, max(tri, 0));
+                float w2m[12];
+#pragma unroll
+                for (int q = 0; q < 12; q++) w2m[q] = p.models[mi].w2m[q];
+                const int sm = S.smooth;
+                const f3 sn = smooth_normal(w2m, nm, T, r.o, r.d, hh.x, hn);
+                hn = ((hm >= 0) & (tri >= 0) & (sm != 0)) ? sn : hn;
+            }
             h.dist = hh.x;
             h.model = hm;
             h.n = hm >= 0 ? hn : mk3(0, 0, 0);
@@ -2667,7 +2733,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             r.d = mk3(b.x, b.y, b.z); r.bounces = __float_as_int(b.w);
             r.c = mk3(c.x, c.y, c.z);
             if (ACCEL == kAccelHitBuffer) {       // traced by k_trace_bvh / k_trace_gf
-                h = get_hit(p, j);
+                h = SMOOTH ? get_hit(p, j, r.o, r.d) : get_hit(p, j);
             } else {
                 h = intersect_scene<ACCEL, BS>(p, r.o, r.d, s_stack + threadIdx.x, s_hs + threadIdx.x);
             }
@@ -3185,7 +3251,13 @@ __global__ __launch_bounds__(kSortWG) void k_sort_scatter(KParams p, int bounce)
 __global__ __launch_bounds__(kBlock) void k_gather_hits(KParams p, int n, float* dist, float* nrm, int* model, int* tri) {
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= n) return;
-    const Hit h = get_hit(p, j);
+    Hit h = get_hit(p, j);
+    if (p.smooth) {      // the slot's ray, where bounce 1's shading pass would read it (pool 0, k_scan's offsets)
+        const int src = slot_source(p, j);
+        const float4 a = p.ray[0][0][src];
+        const float4 b = p.ray[0][1][src];
+        h = get_hit(p, j, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z));
+    }
     dist[j] = h.dist;
     nrm[3 * j] = h.n.x; nrm[3 * j + 1] = h.n.y; nrm[3 * j + 2] = h.n.z;
     model[j] = h.model;
@@ -3375,6 +3447,25 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     PT_HIP(upload(allocs, &env_dev, nullptr, sizeof(EnvRec), stream));
     if (env_on && uploadEnvironment() != 0) return -1;
     kp.env = env_on ? env_dev : nullptr;
+    // smooth shading: the flags as they are now (uploaded with model_shade above) and, only when
+    // some model is smooth, the per-triangle table the hit normal interpolates from
+    kp.smooth = nullptr;
+    bool any_smooth = false;
+    for (const ModelShade& sh : scene.model_shade) any_smooth |= sh.smooth != 0;
+    if (any_smooth) {
+        std::vector<TriShade> tab(std::max<size_t>(scene.triangles.size(), 1), TriShade{});   // record 0 always exists
+        for (size_t t = 0; t < scene.triangles.size(); t++) {
+            TriShade& q = tab[t];
+            std::memcpy(q.v0, &scene.tri_geom[t * 12], 12 * sizeof(float));       // v0, e1, e2 as the traces read them
+            float* nn[3] = {q.n0, q.n1, q.n2};
+            for (int j = 0; j < 3; j++) {
+                const f3 vn = scene.vertices[scene.triangles[t].vertex_indices[j]].normal;
+                nn[j][0] = vn.x; nn[j][1] = vn.y; nn[j][2] = vn.z; nn[j][3] = 0.0f;
+            }
+        }
+        // the copy is enqueued from pageable memory: it is staged before the call returns
+        PT_HIP(upload(allocs, &kp.smooth, tab.data(), tab.size() * sizeof(TriShade), stream));
+    }
     if (external_image) kp.image = ext_image;
     else PT_HIP(upload(allocs, &kp.image, nullptr, (size_t)npix_all * 3 * sizeof(float), stream));
     {
@@ -3652,7 +3743,9 @@ void Renderer::launchTrace(const KParams& k, hipStream_t st, int b) {
 
 template <bool FIRST, int BS>
 static void launch_bounce_bs(int accel, dim3 grid, hipStream_t st, const KParams& kp, int iter, int b) {
-    if (accel == kAccelHitBuffer)
+    if (accel == kAccelHitBuffer && kp.smooth && !FIRST)
+        hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true>), grid, dim3(BS), 0, st, kp, iter, b);
+    else if (accel == kAccelHitBuffer)
         hipLaunchKernelGGL((k_bounce<FIRST, kAccelHitBuffer, BS>), grid, dim3(BS), 0, st, kp, iter, b);
     else if (accel == ACCEL_BVH) hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_BVH, BS>), grid, dim3(BS), 0, st, kp, iter, b);
     else if (accel == ACCEL_GRID_FAST)

@@ -286,6 +286,20 @@ int Scene::addModel(int mesh_index, const float scale[3], const float rot_deg[3]
     return (int)models.size() - 1;
 }
 
+int Scene::setModelSmooth(int model, bool on) {
+    if (model < -1 || model >= (int)models.size()) { last_error = "setModelSmooth: bad model index"; return -1; }
+    for (int i = model < 0 ? 0 : model; i < (model < 0 ? (int)models.size() : model + 1); i++) {
+        models[i].smooth = on;
+        if (model_shade.size() == models.size()) model_shade[i].smooth = on ? 1 : 0;   // built: the flag alone changes
+    }
+    return 0;
+}
+
+int Scene::modelSmooth(int model) const {
+    if (model < 0 || model >= (int)models.size()) return -1;
+    return models[model].smooth ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // Config.txt grammar (PathTracerAP/Config.txt): blank-line separated blocks,
 // first line = keyword.  See DESIGN.md "Scene description".
@@ -486,6 +500,7 @@ int Scene::loadConfig(const std::string& path) {
         }
         float scale[3] = {1, 1, 1}, rot[3] = {0, 0, 0}, tr[3] = {0, 0, 0};
         Mat mat; mat.type = MAT_DIFFUSE; mat.color[0] = mat.color[1] = mat.color[2] = 0.98f;
+        bool smooth = false;
         for (size_t i = first_attr; i < b.size(); i++) {
             std::string key = b[i].substr(0, b[i].find(':'));
             std::string val = b[i].find(':') == std::string::npos ? "" : trim(b[i].substr(b[i].find(':') + 1));
@@ -496,6 +511,11 @@ int Scene::loadConfig(const std::string& path) {
                 mat = it->second;
                 continue;
             }
+            if (key == "shading") {
+                if (val != "smooth" && val != "flat") return fail("bad attribute " + b[i]);
+                smooth = val == "smooth";
+                continue;
+            }
             if (!parse_vec(val, v) || v.size() != 3) return fail("bad attribute " + b[i]);
             float f[3] = {(float)v[0], (float)v[1], (float)v[2]};
             if (key == "translate") std::memcpy(tr, f, sizeof f);
@@ -503,7 +523,9 @@ int Scene::loadConfig(const std::string& path) {
             else if (key == "rotate" || key == "rotateX") std::memcpy(rot, f, sizeof f);  // Config.txt:6 "rotateX:[x,y,z]"
             else return fail("unknown attribute " + key);
         }
-        if (addModel(mesh, scale, rot, tr, mat.type, mat.color) < 0) return -4;
+        const int model = addModel(mesh, scale, rot, tr, mat.type, mat.color);
+        if (model < 0) return -4;
+        models[model].smooth = smooth;
     }
     if (models.empty()) return fail("scene has no MESH/BOX/SPHERE instances");
     return 0;
@@ -621,8 +643,10 @@ void Scene::buildDeviceTables() {
         r.bvh_root = mesh_bvh_root.empty() ? -1 : mesh_bvh_root[m.mesh_index];
         r.bvh4_root = mesh_bvh4_root.empty() ? -1 : mesh_bvh4_root[m.mesh_index];
         ModelShade& sh = model_shade[i];
+        std::memset(&sh, 0, sizeof sh);
         for (int k = 0; k < 3; k++) sh.color[k] = m.mat.color[k];
         sh.mat_type = m.mat.material_type;
+        sh.smooth = m.smooth ? 1 : 0;
         world_box(m, mesh, r.bvh_root, r.wbox);
         // Bounded hit-set collection (ACCEL_GRID_FAST).  A member h whose voxel box the
         // DDA enters at ray parameter tau has its hit within tau + R_h, R_h = the diameter

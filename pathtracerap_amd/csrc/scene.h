@@ -37,6 +37,7 @@ struct Model {                                          // Primitive.h:94-101
     float model_to_world[16];                           // column-major glm::mat4
     float world_to_model[16];
     Material mat;
+    bool smooth = false;                                // setModelSmooth: shade with interpolated vertex normals
 };
 struct Voxel { IndexRange entity_index_range; int entity_type = ENTITY_TRIANGLE; };  // Primitive.h:123-127
 struct Grid {                                           // Primitive.h:129-139
@@ -71,6 +72,10 @@ public:
     // Scene.cpp:32-42 pattern; returns model index.
     int addModel(int mesh_index, const float scale[3], const float rot_deg[3],
                  const float translate[3], int material_type, const float color[3]);
+    // Per-model smooth shading (no counterpart in the reference): model -1 = every model added
+    // so far.  Any time after the model exists; the grid and the BLAS are not touched.
+    int setModelSmooth(int model, bool on);
+    int modelSmooth(int model) const;                   // 0 / 1, negative: bad index
     // addMeshesToGrid (Scene.cpp:318-396) + device tables.  `grid_dim` = GRID_X/Y/Z.
     int build(const int grid_dim[3], bool with_bvh);
     // The BLAS on demand: Renderer::allocateOnGPU calls this for the accels that
@@ -92,7 +97,7 @@ public:
     std::vector<float> tri_geom;      // 12 floats / triangle: v0.xyz,_, e1.xyz,_, e2.xyz,_
     std::vector<float> tri_normal;    // 4 floats / triangle: normalize((n0+n1+n2)*(1/3))
     std::vector<ModelRec> model_recs;
-    std::vector<ModelShade> model_shade;  // per model: material (shading pass)
+    std::vector<ModelShade> model_shade;  // per model: material and smooth flag (shading pass)
     std::vector<BvhNode> bvh_nodes;   // all meshes' BLAS, concatenated
     std::vector<int> bvh_tri_order;   // leaf triangle references (global triangle index)
     std::vector<float> bvh_tri_geom;  // 12 floats / leaf reference: tri_geom in leaf order; w lanes carry
