@@ -318,7 +318,7 @@ void Scene::buildBvh4() {
         const int root = mesh_bvh_root[m];
         if (root < 0) continue;
         // a mesh without triangles gets no 4-wide node either: root -1, which the traces skip at
-        // select (PT_EMPTY_SKIP) and bvh4_traverse returns from at once
+        // select and bvh4_traverse returns from at once
         if (meshes[m].triangle_indices.end_index <= meshes[m].triangle_indices.start_index) continue;
         const size_t n0 = bvh4_nodes.size();
         bool fits = true;
@@ -337,9 +337,6 @@ void Scene::buildBvh4() {
             }
         }
         if (base < 0) base = 0;
-#if defined(PT_LEAF_REL) && PT_LEAF_REL == 0
-        base = 0;                        // absolute leaf links (timing experiments)
-#endif
         // make(b): the 4-wide node for binary node b; returns its index
         std::vector<std::pair<int, int>> work;   // (binary node, 4-wide index) still to fill
         auto alloc = [&](int b) {

@@ -14,10 +14,9 @@
 #include <string>
 #include <vector>
 
+#include "../../include/pathtracer_amd.h"   // PT_NOISE_TILE, pt_environment
 #include "pt_env.h"
 #include "scene.h"
-
-struct pt_environment;           // include/pathtracer_amd.h
 
 namespace pt {
 
@@ -60,7 +59,6 @@ struct KParams {
     const int* per_voxel;
     const Bvh4Node* bvh4;       // the BLAS, 4-wide: every BLAS path walks it (nullptr when the scene has none)
     const float4* bvh_tri_geom; // leaf-ordered triangle records, v0.w = triangle index
-    int top_root[2], top_n[2];  // PT_LDS_TOP builds: the two largest meshes' 4-wide roots, nodes staged (<= kLdsTop)
     int* spill;                 // traversal-stack spill beyond the LDS entries, lane-minor
     int spill_stride;           // lanes in the spill layout
     // frame
@@ -187,8 +185,8 @@ public:
     int noise(int samples, double* mean_err, float* max_tile_err, float* tile_err_host);
     int renderUntil(int first_iter, int min_iters, int max_iters, int check_every, double target,
                     int* iters_done, double* mean_err);
-    int noiseTilesX() const { return (cfg.width + 15) / 16; }      // PT_NOISE_TILE
-    int noiseTilesY() const { return (cfg.height + 15) / 16; }
+    int noiseTilesX() const { return (cfg.width + PT_NOISE_TILE - 1) / PT_NOISE_TILE; }
+    int noiseTilesY() const { return (cfg.height + PT_NOISE_TILE - 1) / PT_NOISE_TILE; }
     // film.hip: variance-guided edge-avoiding denoiser of the accumulated image (no counterpart
     // in the reference); the image and the moments are read only
     int denoise(int samples, int passes, float sigma_l, float sigma_z, float* device_rgb_out, float* host_rgb,

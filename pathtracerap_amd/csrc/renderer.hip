@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <type_traits>
 
 #include "renderer.h"
 
@@ -41,18 +42,11 @@ constexpr int kBlock = 256;
 #ifndef PT_HITCAP
 #define PT_HITCAP 6
 #endif
-#ifndef PT_CERT_MODE
-#define PT_CERT_MODE 1        // k_trace_gf main launch's walk decision: 0 walk_certify only, 1 walk_certify_fast
-                              // first, 2 walk_certify_fast only (the rest goes to the tail launch's exact walk)
-#endif
 #ifndef PT_TRACE_STATS
 #define PT_TRACE_STATS 0      // 1: diagnostic counters / timing ablations (PT_DEBUG_ABLATE); cost registers
 #endif
 #ifndef PT_MINWAVES
 #define PT_MINWAVES 5
-#endif
-#ifndef PT_SEL_MASK
-#define PT_SEL_MASK 1         // k_trace_gf main launch: select steps jump over models a fresh ray's mask rules out
 #endif
 #ifndef PT_NODE_MINLANES
 #define PT_NODE_MINLANES 8    // k_trace_gf: the wave leaves a node step once fewer lanes than this are still at a node
@@ -1353,14 +1347,10 @@ __device__ __forceinline__ int slot_source(const KParams& p, int j) {
 // entries in a global spill area laid out lane-minor (p.spill_stride lanes).
 // The seven float4 loads of a 4-wide node visit (Bvh4Node: planes lo x/y/z, hi x/y/z,
 // links; count is never read): each axis' near and far planes by the slope sign's
-// offset o* (0 or 3).  PT_NODE_OFF32: 32-bit byte offsets from the node array's base,
+// offset o* (0 or 3).  32-bit byte offsets from the node array's base,
 // so the loads take the SGPR base + 32-bit VGPR offset form (one 32-bit add per
 // plane instead of a 64-bit address each; the BLAS is < 4 GB: leaf entries cap a
 // mesh at 2^26 triangles).
-#ifndef PT_NODE_OFF32
-#define PT_NODE_OFF32 1
-#endif
-#if PT_NODE_OFF32
 #define PT_NODE_LOADS(cur, ox, oy, oz)                                                                   \
     const char* __restrict__ nb_ = reinterpret_cast<const char*>(p.bvh4);                                \
     const unsigned nbo_ = (unsigned)(cur) << 7;                                                          \
@@ -1368,13 +1358,6 @@ __device__ __forceinline__ int slot_source(const KParams& p, int j) {
     const float4 NX = ld4_(ox), NY = ld4_(1 + (oy)), NZ = ld4_(2 + (oz));                                \
     const float4 FX = ld4_(3 - (ox)), FY = ld4_(4 - (oy)), FZ = ld4_(5 - (oz));                          \
     const float4 LKf = ld4_(6);
-#else
-#define PT_NODE_LOADS(cur, ox, oy, oz)                                                                   \
-    const float4* __restrict__ n4 = reinterpret_cast<const float4*>(p.bvh4) + 8 * (size_t)(cur);         \
-    const float4 NX = n4[ox], NY = n4[1 + (oy)], NZ = n4[2 + (oz)];                                      \
-    const float4 FX = n4[3 - (ox)], FY = n4[4 - (oy)], FZ = n4[5 - (oz)];                                \
-    const float4 LKf = n4[6];
-#endif
 
 template <int BS, int SCAP = kStack>
 __device__ __forceinline__ void spush_t(int* stack, int* spill, int stride, int sp, int e) {
@@ -1392,20 +1375,11 @@ __device__ __forceinline__ int spop_if(bool take, const int* stack, const int* s
     return v;
 }
 
-#ifndef PT_LEAF_REL
-#define PT_LEAF_REL 1         // 4-wide leaf links relative to ModelRec::leaf_base (0: absolute; timing experiments)
-#endif
-#ifndef PT_EMPTY_SKIP
-#define PT_EMPTY_SKIP 1       // the traces' select steps skip models whose mesh has no triangles
-#endif
 #ifndef PT_LEAF_STEP
 #define PT_LEAF_STEP 2        // leaf triangles tested per leaf step of k_trace_bvh (1..4; k_trace_gf: 1 or 2)
 #endif
 #ifndef PT_BVH_NODE_STEP
 #define PT_BVH_NODE_STEP 4    // k_trace_bvh: node visits per node step (as PT_NODE_STEP)
-#endif
-#ifndef PT_BVH_SEL_MASK
-#define PT_BVH_SEL_MASK 1     // k_trace_bvh: PT_SEL_MASK's candidate mask for the main launch's select steps
 #endif
 #ifndef PT_BVH_LEAF_W
 #define PT_BVH_LEAF_W 4       // k_trace_bvh phase weights (x/4) of leaf and select lane counts against node's
@@ -1516,9 +1490,9 @@ __global__ __launch_bounds__(BS, PT_BVH_MINWAVES) void k_trace_bvh(KParams p, in
     int lf_next = -1;                               // then node lf_next (-1: pop the stack)
     float best = kFMax;
     bool any = false, exhausted = false;
-    // PT_BVH_SEL_MASK: the main launch's select steps jump to the next model a ray can reach
-    // (k_trace_gf's PT_SEL_MASK; the miss test once per ray, the gdist test per candidate)
-    constexpr bool kSelMask = PT_BVH_SEL_MASK && !TAIL && (F & 1);
+    // the main launch's select steps jump to the next model a ray can reach
+    // (k_trace_gf's candidate mask; the miss test once per ray, the gdist test per candidate)
+    constexpr bool kSelMask = !TAIL && (F & 1);
     unsigned cmask = ~0u;
     unsigned long long st_iter = 0, st_node = 0, st_leaf = 0, st_sel = 0;   // PT_DEBUG_ABLATE & 16
     unsigned long long st_busy = 0, st_drain = 0, st_drain_busy = 0;       // busy lanes; iterations after exhaustion
@@ -1689,7 +1663,7 @@ __global__ __launch_bounds__(BS, PT_BVH_MINWAVES) void k_trace_bvh(KParams p, in
                     node_slab(M.wbox, M.wbox + 3, ow, winv, wtn, wtf);
                     if (wtn * dlen > gdist * 1.0001f + 0.01f) continue;
                 } else if (model_culled<ACCEL_BVH>(M, ow, dw, winv, dlen, gdist)) continue;
-                if (PT_EMPTY_SKIP && M.bvh4_root < 0) continue;   // a mesh without triangles: no hit, no BLAS
+                if (M.bvh4_root < 0) continue;   // a mesh without triangles: no hit, no BLAS
                 o = xform12(M.w2m, ow, 1.0f);
                 d = normalize(xform12(M.w2m, dw, 0.0f));
                 const f3 inv = mk3(1 / d.x, 1 / d.y, 1 / d.z);
@@ -1733,7 +1707,7 @@ __global__ __launch_bounds__(BS, PT_BVH_MINWAVES) void k_trace_bvh(KParams p, in
             const int top = spop_if<BS, kStack>(pop, stack, spill, p.spill_stride, sp - 1);
             sp -= pop ? 1 : 0;
             const bool tleaf = pop & (top < 0);
-            const int first = (PT_LEAF_REL ? lbase : 0) + (top & ((1 << kLeafCountShift) - 1));   // mesh-relative entry
+            const int first = lbase + (top & ((1 << kLeafCountShift) - 1));   // mesh-relative entry
             lf_e = tleaf ? first + ((top >> kLeafCountShift) & kMaxLeafCount4) : lf_e;
             lf_i = tleaf ? first : lf_i;
             cur = (pop & !tleaf) ? top : cur;
@@ -1786,7 +1760,7 @@ __global__ __launch_bounds__(BS, PT_BVH_MINWAVES) void k_trace_bvh(KParams p, in
                 sp -= pop ? 1 : 0;
                 const int nx = nhit > 0 ? ent[0] : top;
                 const bool leaf = !model_done & (nx < 0);
-                const int first = (PT_LEAF_REL ? lbase : 0) + (nx & ((1 << kLeafCountShift) - 1));
+                const int first = lbase + (nx & ((1 << kLeafCountShift) - 1));
                 lf_i = leaf ? first : lf_i;
                 lf_e = leaf ? first + ((nx >> kLeafCountShift) & kMaxLeafCount4) : lf_e;
                 cur = (!model_done & !leaf) ? nx : cur;
@@ -1855,13 +1829,7 @@ __global__ __launch_bounds__(BS, PT_BVH_MINWAVES) void k_trace_bvh(KParams p, in
 #ifndef PT_GF_TAIL_MINWAVES
 #define PT_GF_TAIL_MINWAVES 4 // the same for the tail launches (k_trace_gf<..., TAIL = true>)
 #endif
-#ifndef PT_LDS_TOP
-#define PT_LDS_TOP 0          // k_trace_gf: top 4-wide nodes per mesh staged in LDS (experiment; 0 = off)
-#endif
-#ifndef PT_LDS_TOP_MESHES
-#define PT_LDS_TOP_MESHES 2   // ... of the largest one or two meshes
-#endif
-constexpr int kGfStack = PT_GF_STACK, kGfHitCap = PT_GF_HITCAP, kLdsTop = PT_LDS_TOP, kLdsTopMeshes = PT_LDS_TOP_MESHES;
+constexpr int kGfStack = PT_GF_STACK, kGfHitCap = PT_GF_HITCAP;
 // 4-wide traversal: at most 3 pushes per node on a path of at most kMaxBvhDepth + 1 nodes (an unopened
 // slot keeps its binary level, so a 4-wide path can be as long as a binary one)
 static_assert(3 * (kMaxBvhDepth + 1) + 1 <= kGfStack + kSpillEntries,
@@ -1971,12 +1939,9 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
     __shared__ int4 s_hs[kGfHitCap * BS];
     constexpr int kModelsHere = (F & 1) ? ((F & 32) ? kLdsModelsWide : kLdsModelsGf) : 1;
     __shared__ ModelRec s_models[kModelsHere];
-    // PT_LDS_TOP (experiment, default 0): the first kLdsTop 4-wide nodes (breadth-first: the
-    // root, then level 1, ...) of the two largest meshes (KParams::top_root / top_n) in LDS
-    __shared__ float4 s_top[kLdsTop > 0 ? kLdsTopMeshes * kLdsTop * 8 : 1];
-    // PT_SEL_MASK: per lane, the models whose world box the ray can reach (gdist aside),
+    // per lane, the models whose world box the ray can reach (gdist aside),
     // found once per ray so later select steps jump to the next candidate
-    constexpr bool kSelMask = PT_SEL_MASK && !TAIL && (F & 1);
+    constexpr bool kSelMask = !TAIL && (F & 1);
     // node steps: the in-place variant (F & 16: one pipeline, one launch alone on the chip)
     // measured best at 4 visits (4-wide nodes) without the minimum; the
     // hand-on variants of several pipelines at PT_NODE_STEP / PT_NODE_MINLANES
@@ -2016,15 +1981,6 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
         for (int i = threadIdx.x; i < nw; i += BS) dst[i] = src[i];
         __syncthreads();
     }
-    if (kLdsTop > 0) {
-        const float4* nodes4 = reinterpret_cast<const float4*>(p.bvh4);
-        for (int i = threadIdx.x; i < kLdsTopMeshes * kLdsTop * 8; i += BS) {
-            constexpr int kT = kLdsTop > 0 ? kLdsTop : 1;
-            const int m = i / (kT * 8), k = (i / 8) % kT;
-            s_top[i] = k < p.top_n[m] ? nodes4[8 * (size_t)(p.top_root[m] + k) + (i & 7)] : make_float4(0, 0, 0, 0);
-        }
-        __syncthreads();
-    }
     const ModelRec* models = lds_models ? s_models : p.models;
     const int n = p.n_live[bounce];
     const int in_buf = (bounce + 1) & 1;
@@ -2043,7 +1999,7 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
     int lf_i = 0, lf_e = 0, lf2_i = 0, lf2_e = 0, lf_next = -1;
     int lbase = 0;                                  // ModelRec::leaf_base of the model being traced
     bool exhausted = false;
-    unsigned cmask = 0;                            // PT_SEL_MASK: candidate models of the lane's ray
+    unsigned cmask = 0;                            // kSelMask: candidate models of the lane's ray
     unsigned long long st_iter = 0, st_node = 0, st_leaf = 0, st_walk = 0, st_sel = 0;   // PT_DEBUG_ABLATE & 16
     unsigned long long st_busy = 0, st_drain = 0, st_drain_busy = 0;       // busy lanes; iterations after exhaustion
     unsigned long long it_node = 0, it_leaf = 0, it_walk = 0, it_sel = 0;
@@ -2241,7 +2197,7 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
                     node_slab(M.wbox, M.wbox + 3, ow, winv, wtn, wtf);
                     if (wtn * dlen > gdist * 1.0001f + 0.01f) continue;
                 } else if (model_culled<ACCEL_GRID_FAST>(M, ow, dw, winv, dlen, gdist)) continue;
-                if (PT_EMPTY_SKIP && M.bvh4_root < 0) continue;   // a mesh without triangles: no hit, no BLAS
+                if (M.bvh4_root < 0) continue;   // a mesh without triangles: no hit, no BLAS
                 o = xform12(M.w2m, ow, 1.0f);
                 d = normalize(xform12(M.w2m, dw, 0.0f));
                 const f3 inv = mk3(1 / d.x, 1 / d.y, 1 / d.z);
@@ -2344,7 +2300,7 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
                 const int top = spop_if<BS, kGfStack>(pop, stack, spill, p.spill_stride, sp - 1);
                 sp -= pop ? 1 : 0;
                 const bool tleaf = pop & (top < 0);
-                const int first = (PT_LEAF_REL ? lbase : 0) + (top & ((1 << kLeafCountShift) - 1));   // mesh-relative entry
+                const int first = lbase + (top & ((1 << kLeafCountShift) - 1));   // mesh-relative entry
                 lf_e = tleaf ? first + ((top >> kLeafCountShift) & kMaxLeafCount4) : lf_e;
                 lf_i = tleaf ? first : lf_i;
                 cur = (pop & !tleaf) ? top : cur;
@@ -2357,27 +2313,7 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
                 // load each axis' near and far planes directly (lo for a positive slope), so the
                 // entries and exits come without min / max, and the voxel-grown entry is one fma
                 const int ox = ninv.x < 0.0f ? 3 : 0, oy = ninv.y < 0.0f ? 3 : 0, oz = ninv.z < 0.0f ? 3 : 0;
-#if PT_LDS_TOP
-                const int rel0_ = cur - p.top_root[0], rel1_ = cur - p.top_root[1];
-                const bool in0_ = (unsigned)rel0_ < (unsigned)p.top_n[0];
-                const bool in1_ = kLdsTopMeshes > 1 && (unsigned)rel1_ < (unsigned)p.top_n[1];
-                float4 NX, NY, NZ, FX, FY, FZ, LKf;
-                if (in0_ | in1_) {
-                    const float4* q_ = s_top + 8 * (in0_ ? rel0_ : kLdsTop + rel1_);
-                    NX = q_[ox]; NY = q_[1 + oy]; NZ = q_[2 + oz];
-                    FX = q_[3 - ox]; FY = q_[4 - oy]; FZ = q_[5 - oz];
-                    LKf = q_[6];
-                } else {
-                    const char* __restrict__ nb_ = reinterpret_cast<const char*>(p.bvh4);
-                    const unsigned nbo_ = (unsigned)cur << 7;
-                    auto ld4_ = [&](int q) { return *reinterpret_cast<const float4*>(nb_ + (nbo_ + 16u * (unsigned)q)); };
-                    NX = ld4_(ox); NY = ld4_(1 + oy); NZ = ld4_(2 + oz);
-                    FX = ld4_(3 - ox); FY = ld4_(4 - oy); FZ = ld4_(5 - oz);
-                    LKf = ld4_(6);
-                }
-#else
                 PT_NODE_LOADS(cur, ox, oy, oz)
-#endif
                 const float pnx[4] = {NX.x, NX.y, NX.z, NX.w}, pny[4] = {NY.x, NY.y, NY.z, NY.w};
                 const float pnz[4] = {NZ.x, NZ.y, NZ.z, NZ.w}, pfx[4] = {FX.x, FX.y, FX.z, FX.w};
                 const float pfy[4] = {FY.x, FY.y, FY.z, FY.w}, pfz[4] = {FZ.x, FZ.y, FZ.z, FZ.w};
@@ -2435,7 +2371,7 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
                 sp -= pop ? 1 : 0;
                 const int nx = nhit > 0 ? ent[0] : top;       // the entry to go on with (when not collected)
                 const bool leaf = !collected & (nx < 0);
-                const int first = (PT_LEAF_REL ? lbase : 0) + (nx & ((1 << kLeafCountShift) - 1));
+                const int first = lbase + (nx & ((1 << kLeafCountShift) - 1));
                 lf_i = leaf ? first : lf_i;
                 lf_e = leaf ? first + ((nx >> kLeafCountShift) & kMaxLeafCount4) : lf_e;
                 cur = (!collected & !leaf) ? nx : cur;
@@ -2485,13 +2421,13 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
                 bool ok = false;
                 // ninv (1/d clamped to +-1e30, set at select) is the exact 1/d when no slope is clamped
                 const bool exact_inv = (absr(ninv.x) < 1e30f) & (absr(ninv.y) < 1e30f) & (absr(ninv.z) < 1e30f);
-                if (PT_CERT_MODE >= 1 && pblk < 0 && exact_inv)
+                if (pblk < 0 && exact_inv)
                     ok = walk_certify_fast<kGfHitCap>(p, M, d, ninv, pt, t_box, lds_get, nh, tmin, win, tri);
                 if (PT_TRACE_STATS && (p.debug & 4)) {
                     atomicAdd(p.segments + 42 + kMaxBounceCounters, 1ull);
                     if (ok) atomicAdd(p.segments + 40 + kMaxBounceCounters, 1ull);
                 }
-                if (PT_CERT_MODE <= 1 && !ok && pblk < 0) {
+                if (!ok && pblk < 0) {
                     const f3 inv = mk3(1 / d.x, 1 / d.y, 1 / d.z);
                     ok = walk_certify<kGfHitCap>(p, M, d, inv, pt, t_box, lds_get, nh, tmin, win, tri);
                     if (PT_TRACE_STATS && (p.debug & 4) && ok) atomicAdd(p.segments + 41 + kMaxBounceCounters, 1ull);
@@ -2601,6 +2537,86 @@ __global__ __launch_bounds__(BS, TAIL ? PT_GF_TAIL_MINWAVES : PT_GF_MINWAVES) vo
     }
 }
 
+// ---- building blocks of the kernels that write a bounce's surviving rays ----
+
+// The ray sort's key of a ray (defined with the sort kernels below).  Every kernel that
+// writes a surviving ray into a pool stores the key of the o and d it holds in registers
+// beside it, so k_sort_hist reads 2 bytes per ray instead of the two ray planes.
+// One key buffer per pipeline: bounce b's scatter has finished on the stream before
+// k_bounce(b) overwrites the keys.
+__device__ __forceinline__ int sort_key(const KParams& p, f3 o, f3 d);
+__device__ __forceinline__ void put_sort_key(const KParams& p, int dst, f3 o, f3 d) {
+    if (p.sort_key) p.sort_key[dst] = (unsigned short)sort_key(p, o, d);
+}
+
+// A ray into slot dst of pool buf: the three planes and its sort key.
+__device__ __forceinline__ void store_ray(const KParams& p, int buf, int dst, f3 o, f3 d, f3 c, int pixel, int bounces) {
+    p.ray[buf][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(pixel));
+    p.ray[buf][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(bounces));
+    p.ray[buf][2][dst] = make_float4(c.x, c.y, c.z, 0.0f);
+    put_sort_key(p, dst, o, d);
+}
+
+// The ray at index src of pool buf.  PLANES = 2: (o, pixel) and (d, bounces) only; c is not loaded.
+template <int PLANES = 3>
+__device__ __forceinline__ RayState load_ray(const KParams& p, int buf, int src) {
+    RayState r;
+    const float4 a = p.ray[buf][0][src];
+    const float4 b = p.ray[buf][1][src];
+    r.o = mk3(a.x, a.y, a.z); r.pixel = __float_as_int(a.w);
+    r.d = mk3(b.x, b.y, b.z); r.bounces = __float_as_int(b.w);
+    if (PLANES > 2) {
+        const float4 c = p.ray[buf][2][src];
+        r.c = mk3(c.x, c.y, c.z);
+    }
+    return r;
+}
+
+// Pixel j's path at its cached primary hit: the camera ray with throughput 1 and every bounce left.
+__device__ __forceinline__ void first_hit_state(const KParams& p, int j, RayState& r, Hit& h) {
+    camera_ray(p, j, r.o, r.d);
+    r.c = mk3(1.0f, 1.0f, 1.0f);
+    r.pixel = j;
+    r.bounces = p.max_bounces;
+    const float4 ch = p.cache_hit[j];
+    h.dist = ch.x;
+    h.n = mk3(ch.y, ch.z, ch.w);
+    h.model = p.cache_model[j];
+}
+
+// Whether pixel j lies in a tile the mask keeps (tile-masked sampling; the noise estimate's tiles).
+constexpr int kNoiseTileShift = __builtin_ctz(PT_NOISE_TILE);
+static_assert((1 << kNoiseTileShift) == PT_NOISE_TILE, "tile_active shifts by log2(PT_NOISE_TILE)");
+__device__ __forceinline__ bool tile_active(const unsigned char* __restrict__ tile_mask, int tiles_x, int width, int j) {
+    const int y = j / width, x = j - y * width;
+    return tile_mask[(y >> kNoiseTileShift) * tiles_x + (x >> kNoiseTileShift)] != 0;
+}
+
+// Block-local stable compaction (ballot + wave prefix), order == lane order: the lane's
+// offset among the block's alive lanes, their number in `total`.  Every lane of the block
+// calls it: above one wave the waves exchange their counts through s_wave[BS / 64].
+template <int BS>
+__device__ __forceinline__ int block_compact(bool alive, int* s_wave, int& total) {
+    const unsigned long long m = __ballot(alive);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    int base = 0;
+    total = 0;
+    if (BS > 64) {
+        if (lane == 0) s_wave[wid] = __popcll(m);
+        __syncthreads();
+    } else {
+        total = __popcll(m);
+    }
+#pragma unroll
+    for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
+        const int c = s_wave[w];
+        base += (w < wid) ? c : 0;
+        total += c;
+    }
+    return base + rank;
+}
+
 // Rays k_trace_gf deferred (LDS hit-set overflow): the fused path's
 // intersect_scene<ACCEL_GRID_FAST> (LDS tiers, global pool, list-walking DDA),
 // one lane per ray.
@@ -2617,27 +2633,12 @@ __global__ __launch_bounds__(BS) void k_trace_deferred(KParams p, int bounce) {
     for (int q = blockIdx.x * BS + threadIdx.x; q < cnt; q += gridDim.x * BS) {
         const int j = p.defer_slots[q];
         const int src = p.slot_src ? p.slot_src[j] : slot_source(p, j);   // this bounce's scatter ran before the trace
-        const float4 a = p.ray[in_buf][0][src];
-        const float4 b = p.ray[in_buf][1][src];
+        const RayState r = load_ray<2>(p, in_buf, src);
         float gdist;
         int gmodel, gtri;
-        intersect_scene_g<ACCEL_GRID_FAST, BS>(p, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), s_stack + threadIdx.x,
-                                               s_hs + threadIdx.x, gdist, gmodel, gtri);
+        intersect_scene_g<ACCEL_GRID_FAST, BS>(p, r.o, r.d, s_stack + threadIdx.x, s_hs + threadIdx.x, gdist, gmodel, gtri);
         put_hit(p, j, gdist, gmodel, gtri);
     }
-}
-
-// The ray sort's key of a ray (defined with the sort kernels below).  PT_WRITER_KEYS: every
-// kernel that writes a surviving ray into a pool stores the key of the o and d it holds in
-// registers beside it, so k_sort_hist reads 2 bytes per ray instead of the two ray planes.
-// One key buffer per pipeline: bounce b's scatter has finished on the stream before
-// k_bounce(b) overwrites the keys.  0: k_sort_hist computes the keys (A/B builds).
-#ifndef PT_WRITER_KEYS
-#define PT_WRITER_KEYS 1
-#endif
-__device__ __forceinline__ int sort_key(const KParams& p, f3 o, f3 d);
-__device__ __forceinline__ void put_sort_key(const KParams& p, int dst, f3 o, f3 d) {
-    if (PT_WRITER_KEYS && p.sort_key) p.sort_key[dst] = (unsigned short)sort_key(p, o, d);
 }
 
 // One bounce for every live ray: gather -> intersect -> shade -> compact / accumulate.
@@ -2671,12 +2672,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             const int src = p.slot_src[j];
             const float4 hh = p.hit4[j];
             const int hm = p.hitm[j];
-            const float4 a = p.ray[in_buf][0][src];
-            const float4 b = p.ray[in_buf][1][src];
-            const float4 c = p.ray[in_buf][2][src];
-            r.o = mk3(a.x, a.y, a.z); r.pixel = __float_as_int(a.w);
-            r.d = mk3(b.x, b.y, b.z); r.bounces = __float_as_int(b.w);
-            r.c = mk3(c.x, c.y, c.z);
+            r = load_ray(p, in_buf, src);
             // get_hit's values.  The second group's loads are unconditional, a miss's (and
             // a hit without a triangle's) at index 0, which exists: a live ray at bounce >= 1
             // means some triangle of some model was hit.  Under `if (hm >= 0)` the compiler
@@ -2710,14 +2706,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
         }
     } else if (active) {
         if (FIRST) {
-            camera_ray(p, j, r.o, r.d);
-            r.c = mk3(1.0f, 1.0f, 1.0f);
-            r.pixel = j;
-            r.bounces = p.max_bounces;
-            const float4 ch = p.cache_hit[j];
-            h.dist = ch.x;
-            h.n = mk3(ch.y, ch.z, ch.w);
-            h.model = p.cache_model[j];
+            first_hit_state(p, j, r, h);
         } else {
             // dense slot j -> (source block b, rank) via the scan of the previous bounce
             int lo = p.dst_start[chunk], hi = p.dst_start[chunk + 1];
@@ -2725,13 +2714,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
                 const int mid = (lo + hi + 1) >> 1;
                 if (p.blk_off[mid] <= j) lo = mid; else hi = mid - 1;
             }
-            const int src = lo * BS + (j - p.blk_off[lo]);
-            const float4 a = p.ray[in_buf][0][src];
-            const float4 b = p.ray[in_buf][1][src];
-            const float4 c = p.ray[in_buf][2][src];
-            r.o = mk3(a.x, a.y, a.z); r.pixel = __float_as_int(a.w);
-            r.d = mk3(b.x, b.y, b.z); r.bounces = __float_as_int(b.w);
-            r.c = mk3(c.x, c.y, c.z);
+            r = load_ray(p, in_buf, lo * BS + (j - p.blk_off[lo]));
             if (ACCEL == kAccelHitBuffer) {       // traced by k_trace_bvh / k_trace_gf
                 h = SMOOTH ? get_hit(p, j, r.o, r.d) : get_hit(p, j);
             } else {
@@ -2759,30 +2742,9 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             px[2] += 1.0f * sqrtf(r.c.z);
         }
     }
-    // Block-local stable compaction (ballot + wave prefix), order == slot order.
-    const unsigned long long m = __ballot(alive);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    int base = 0, total = 0;
-    if (BS > 64) {
-        if (lane == 0) s_wave[wid] = __popcll(m);
-        __syncthreads();
-    } else {
-        total = __popcll(m);
-    }
-#pragma unroll
-    for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
-        const int c = s_wave[w];
-        base += (w < wid) ? c : 0;
-        total += c;
-    }
-    if (alive) {
-        const int dst = j0 + base + rank;
-        p.ray[out_buf][0][dst] = make_float4(r.o.x, r.o.y, r.o.z, __int_as_float(r.pixel));
-        p.ray[out_buf][1][dst] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(r.bounces));
-        p.ray[out_buf][2][dst] = make_float4(r.c.x, r.c.y, r.c.z, 0.0f);
-        put_sort_key(p, dst, r.o, r.d);
-    }
+    int total;                                 // survivors keep slot order
+    const int at = block_compact<BS>(alive, s_wave, total);
+    if (alive) store_ray(p, out_buf, j0 + at, r.o, r.d, r.c, r.pixel, r.bounces);
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
 
@@ -2804,22 +2766,11 @@ __global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, in
     if (j0 >= n) return;                       // whole block idle (uniform)
     const int j = j0 + threadIdx.x;
     const bool inside = j < n;
-    bool active = false;
-    if (inside) {
-        const int y = j / p.width, x = j - y * p.width;
-        active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
-    }
+    const bool active = inside && tile_active(tile_mask, tiles_x, p.width, j);
     RayState r;
     if (active) {
         Hit h;
-        camera_ray(p, j, r.o, r.d);
-        r.c = mk3(1.0f, 1.0f, 1.0f);
-        r.pixel = j;
-        r.bounces = p.max_bounces;
-        const float4 ch = p.cache_hit[j];
-        h.dist = ch.x;
-        h.n = mk3(ch.y, ch.z, ch.w);
-        h.model = p.cache_model[j];
+        first_hit_state(p, j, r, h);
         shade(p, r, h, iter, j);
     }
     const bool alive = active && r.bounces > 0;
@@ -2829,45 +2780,22 @@ __global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, in
         cp[1] = active ? 1.0f * sqrtf(r.c.y) : 0.0f;
         cp[2] = active ? 1.0f * sqrtf(r.c.z) : 0.0f;
     }
-    const unsigned long long m = __ballot(alive);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    int base = 0, total = 0;
-    if (BS > 64) {
-        if (lane == 0) s_wave[wid] = __popcll(m);
-        __syncthreads();
-    } else {
-        total = __popcll(m);
-    }
-#pragma unroll
-    for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
-        const int c = s_wave[w];
-        base += (w < wid) ? c : 0;
-        total += c;
-    }
-    if (alive) {
-        const int dst = j0 + base + rank;
-        p.ray[0][0][dst] = make_float4(r.o.x, r.o.y, r.o.z, __int_as_float(r.pixel));
-        p.ray[0][1][dst] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(r.bounces));
-        p.ray[0][2][dst] = make_float4(r.c.x, r.c.y, r.c.z, 0.0f);
-        put_sort_key(p, dst, r.o, r.d);
-    }
+    int total;
+    const int at = block_compact<BS>(alive, s_wave, total);
+    if (alive) store_ray(p, 0, j0 + at, r.o, r.d, r.c, r.pixel, r.bounces);
     if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
 }
 
-// Bounce 0 of a pixel-jittered iteration (pt_renderer_set_pixel_jitter): one lane per
-// launched pixel writes its camera ray through a point of the pixel drawn from
-// (iteration, pixel), as bounce 0's survivor, into pool 0 -- nothing is intersected or
-// shaded here; bounce 1's trace finds the primary hit.  The two draws seed with depths
-// max_bounces + 1 and + 2, which shade() never uses (it seeds with 1 .. max_bounces),
-// and with the pixel index, so the offset does not depend on masks, pipelines or ranks.
+// Bounce 0 of an iteration whose camera rays are generated: one lane per launched pixel
+// writes make_ray(x, y, j)'s ray (origin, direction), as bounce 0's survivor, into pool 0 --
+// nothing is intersected or shaded here; bounce 1's trace finds the primary hit.
 // Unmasked: every lane of a block emits, so the destination is the pixel index and the
 // block's count its pixel count.  MASKED: k_bounce_masked's per-lane tile byte and
 // ballot compaction; a pixel of an inactive tile emits nothing and writes contribution
 // 0.0.  Reads nothing but the mask; writes 48 bytes per emitted ray.
-template <int BS, bool MASKED>
-__global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float width,
-                                                    const unsigned char* __restrict__ tile_mask, int tiles_x) {
+template <int BS, bool MASKED, class MakeRay>
+__device__ __forceinline__ void gen_rays(const KParams& p, const unsigned char* __restrict__ tile_mask, int tiles_x,
+                                         MakeRay make_ray) {
     __shared__ int s_wave[MASKED ? BS / 64 : 1];
     const int n = p.npix;
     const int chunk = blockIdx.x;
@@ -2879,33 +2807,31 @@ __global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float wi
     bool active = inside;
     int dst = j, total = min(BS, n - j0);
     if (MASKED) {
-        if (inside) active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
+        if (inside) active = tile_active(tile_mask, tiles_x, p.width, j);
         if (inside && !active) {
             float* cp = p.contrib + 3 * (size_t)j;
             cp[0] = 0.0f;
             cp[1] = 0.0f;
             cp[2] = 0.0f;
         }
-        const unsigned long long m = __ballot(active);
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        int base = 0;
-        total = 0;
-        if (BS > 64) {
-            if (lane == 0) s_wave[wid] = __popcll(m);
-            __syncthreads();
-        } else {
-            total = __popcll(m);
-        }
-#pragma unroll
-        for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
-            const int c = s_wave[w];
-            base += (w < wid) ? c : 0;
-            total += c;
-        }
-        dst = j0 + base + rank;
+        dst = j0 + block_compact<BS>(active, s_wave, total);
     }
     if (active) {
+        f3 o, d;
+        make_ray(x, y, j, o, d);
+        store_ray(p, 0, dst, o, d, mk3(1.0f, 1.0f, 1.0f), j, p.max_bounces);
+    }
+    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+}
+
+// gen_rays for the legacy camera under pixel jitter (pt_renderer_set_pixel_jitter): the ray
+// through a point of the pixel drawn from (iteration, pixel).  The two draws seed with depths
+// max_bounces + 1 and + 2, which shade() never uses (it seeds with 1 .. max_bounces),
+// and with the pixel index, so the offset does not depend on masks, pipelines or ranks.
+template <int BS, bool MASKED>
+__global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float width,
+                                                    const unsigned char* __restrict__ tile_mask, int tiles_x) {
+    gen_rays<BS, MASKED>(p, tile_mask, tiles_x, [&](int x, int y, int j, f3& o, f3& d) {
         Rng rx = Rng::make(iter, j, p.max_bounces + 1);
         Rng ry = Rng::make(iter, j, p.max_bounces + 2);
         const float ux = rx.u01(), uy = ry.u01();
@@ -2913,65 +2839,22 @@ __global__ __launch_bounds__(BS) void k_gen_jitter(KParams p, int iter, float wi
         const float fy = (float)y + width * (uy - 0.5f);
         const float wx = (float)(p.plane_x0 + (double)(fx * p.step_x));
         const float wy = (float)(p.plane_y0 + (double)(fy * p.step_y));
-        const f3 o = mk3(p.cam_x, p.cam_y, p.cam_z);
-        const f3 d = mk3(wx, wy, p.plane_z) - o;
-        p.ray[0][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(j));
-        p.ray[0][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(p.max_bounces));
-        p.ray[0][2][dst] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-        put_sort_key(p, dst, o, d);
-    }
-    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+        o = mk3(p.cam_x, p.cam_y, p.cam_z);
+        d = mk3(wx, wy, p.plane_z) - o;
+    });
 }
 
-// k_gen_jitter for the free camera (pt_renderer_set_camera): bounce 0 of an iteration whose
+// gen_rays for the free camera (pt_renderer_set_camera): bounce 0 of an iteration whose
 // rays are generated because the pixel jitter is on (jit, a kernel argument: wave-uniform)
 // or the camera has a lens (lens_radius > 0, a uniform load).  The point of the plane in
 // focus is camera_point(fx, fy), with k_gen_jitter's (fx, fy) under the jitter and the
 // pixel's own (x, y) without it (no draw is made then); a lens moves the origin to a point
 // of its disc drawn from depths max_bounces + 3 and + 4, two more that shade() never seeds
-// with, and the pixel index.  The block layout, the mask and the compaction are
-// k_gen_jitter's, which keeps its own code for the legacy camera.
+// with, and the pixel index.
 template <int BS, bool MASKED>
 __global__ __launch_bounds__(BS) void k_gen_camera(KParams p, int iter, int jit, float width,
                                                     const unsigned char* __restrict__ tile_mask, int tiles_x) {
-    __shared__ int s_wave[MASKED ? BS / 64 : 1];
-    const int n = p.npix;
-    const int chunk = blockIdx.x;
-    const int j0 = chunk * BS;
-    if (j0 >= n) return;                       // whole block idle (uniform)
-    const int j = j0 + threadIdx.x;
-    const bool inside = j < n;
-    const int y = j / p.width, x = j - y * p.width;
-    bool active = inside;
-    int dst = j, total = min(BS, n - j0);
-    if (MASKED) {
-        if (inside) active = tile_mask[(y >> 4) * tiles_x + (x >> 4)] != 0;        // PT_NOISE_TILE = 16
-        if (inside && !active) {
-            float* cp = p.contrib + 3 * (size_t)j;
-            cp[0] = 0.0f;
-            cp[1] = 0.0f;
-            cp[2] = 0.0f;
-        }
-        const unsigned long long m = __ballot(active);
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        int base = 0;
-        total = 0;
-        if (BS > 64) {
-            if (lane == 0) s_wave[wid] = __popcll(m);
-            __syncthreads();
-        } else {
-            total = __popcll(m);
-        }
-#pragma unroll
-        for (int w = 0; w < (BS > 64 ? BS / 64 : 0); w++) {
-            const int c = s_wave[w];
-            base += (w < wid) ? c : 0;
-            total += c;
-        }
-        dst = j0 + base + rank;
-    }
-    if (active) {
+    gen_rays<BS, MASKED>(p, tile_mask, tiles_x, [&](int x, int y, int j, f3& o, f3& d) {
         const CameraRec& c = *p.camera;
         float fx = (float)x, fy = (float)y;
         if (jit) {
@@ -2982,7 +2865,7 @@ __global__ __launch_bounds__(BS) void k_gen_camera(KParams p, int iter, int jit,
             fy = (float)y + width * (uy - 0.5f);
         }
         const f3 t = camera_point(c, fx, fy);
-        f3 o = mk3(c.origin[0], c.origin[1], c.origin[2]);
+        o = mk3(c.origin[0], c.origin[1], c.origin[2]);
         if (c.lens_radius > 0.0f) {
             Rng r1 = Rng::make(iter, j, p.max_bounces + 3);
             Rng r2 = Rng::make(iter, j, p.max_bounces + 4);
@@ -2995,13 +2878,8 @@ __global__ __launch_bounds__(BS) void k_gen_camera(KParams p, int iter, int jit,
             o = mk3((c.origin[0] + a * c.lens_u[0]) + b * c.lens_v[0], (c.origin[1] + a * c.lens_u[1]) + b * c.lens_v[1],
                     (c.origin[2] + a * c.lens_u[2]) + b * c.lens_v[2]);
         }
-        const f3 d = t - o;
-        p.ray[0][0][dst] = make_float4(o.x, o.y, o.z, __int_as_float(j));
-        p.ray[0][1][dst] = make_float4(d.x, d.y, d.z, __int_as_float(p.max_bounces));
-        p.ray[0][2][dst] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-        put_sort_key(p, dst, o, d);
-    }
-    if (threadIdx.x == 0) p.blk_cnt[chunk] = total;
+        d = t - o;
+    });
 }
 
 // pt_renderer_set_camera after allocate_on_gpu: the new view, by value, into the renderer's
@@ -3148,7 +3026,7 @@ __device__ __forceinline__ int sort_key(const KParams& p, f3 o, f3 d) {
 // Rays entering bounce `bounce` sit at source index i = c*chunk + r (r < blk_cnt[c]) of
 // the previous bounce's pool; dense slot j = blk_off[c] + r.
 // COMPUTE: the keys are computed here from the ray planes and stored (rays the host
-// uploaded: the trace_rays hook; PT_WRITER_KEYS=0 builds); else the kernel that wrote
+// uploaded: the trace_rays hook); else the kernel that wrote
 // the rays left them in p.sort_key (put_sort_key).
 template <bool COMPUTE>
 __global__ __launch_bounds__(kSortWG) void k_sort_hist(KParams p, int bounce) {
@@ -3168,9 +3046,8 @@ __global__ __launch_bounds__(kSortWG) void k_sort_hist(KParams p, int bounce) {
             if (r < p.blk_cnt[c]) {
                 int key;
                 if (COMPUTE) {
-                    const float4 a = p.ray[in_buf][0][i];
-                    const float4 b = p.ray[in_buf][1][i];
-                    key = sort_key(p, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z));
+                    const RayState r = load_ray<2>(p, in_buf, i);
+                    key = sort_key(p, r.o, r.d);
                     p.sort_key[i] = (unsigned short)key;
                 } else {
                     key = p.sort_key[i];
@@ -3253,10 +3130,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_hits(KParams p, int n, float*
     if (j >= n) return;
     Hit h = get_hit(p, j);
     if (p.smooth) {      // the slot's ray, where bounce 1's shading pass would read it (pool 0, k_scan's offsets)
-        const int src = slot_source(p, j);
-        const float4 a = p.ray[0][0][src];
-        const float4 b = p.ray[0][1][src];
-        h = get_hit(p, j, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z));
+        const RayState r = load_ray<2>(p, 0, slot_source(p, j));
+        h = get_hit(p, j, r.o, r.d);
     }
     dist[j] = h.dist;
     nrm[3 * j] = h.n.x; nrm[3 * j + 1] = h.n.y; nrm[3 * j + 2] = h.n.z;
@@ -3393,22 +3268,6 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     kp.bvh4 = nullptr;
     if (!scene.bvh4_nodes.empty())
         PT_HIP(upload(allocs, &kp.bvh4, scene.bvh4_nodes.data(), scene.bvh4_nodes.size() * sizeof(Bvh4Node), stream));
-    {   // PT_LDS_TOP: the two meshes with the most 4-wide nodes (the one after a root's range bounds it)
-        std::vector<std::pair<int, int>> ms;   // (node count, root)
-        std::vector<int> roots;
-        for (int r : scene.mesh_bvh4_root) if (r >= 0) roots.push_back(r);
-        std::sort(roots.begin(), roots.end());
-        roots.erase(std::unique(roots.begin(), roots.end()), roots.end());
-        for (size_t i = 0; i < roots.size(); i++) {
-            const int end = i + 1 < roots.size() ? roots[i + 1] : (int)scene.bvh4_nodes.size();
-            ms.push_back({end - roots[i], roots[i]});
-        }
-        std::sort(ms.rbegin(), ms.rend());
-        for (int m = 0; m < 2; m++) {
-            kp.top_root[m] = m < (int)ms.size() ? ms[m].second : 0;
-            kp.top_n[m] = m < (int)ms.size() ? std::min(ms[m].first, kLdsTop) : 0;
-        }
-    }
     PT_HIP(upload(allocs, &kp.bvh_tri_geom, scene.bvh_tri_geom.data(), scene.bvh_tri_geom.size() * sizeof(float), stream));
 
     kp.width = cfg.width;
@@ -3753,31 +3612,32 @@ static void launch_bounce_bs(int accel, dim3 grid, hipStream_t st, const KParams
     else hipLaunchKernelGGL((k_bounce<FIRST, ACCEL_GRID, BS>), grid, dim3(BS), 0, st, kp, iter, b);
 }
 
-void Renderer::launchBounce(const KParams& k, hipStream_t st, bool first, dim3 grid, int iter, int b, int accel) {
-    switch (k.chunk) {
-        case 64:
-            if (first) launch_bounce_bs<true, 64>(accel, grid, st, k, iter, b);
-            else launch_bounce_bs<false, 64>(accel, grid, st, k, iter, b);
-            break;
-        case 128:
-            if (first) launch_bounce_bs<true, 128>(accel, grid, st, k, iter, b);
-            else launch_bounce_bs<false, 128>(accel, grid, st, k, iter, b);
-            break;
-        default:
-            if (first) launch_bounce_bs<true, 256>(accel, grid, st, k, iter, b);
-            else launch_bounce_bs<false, 256>(accel, grid, st, k, iter, b);
-            break;
+// The bounce kernels are instantiated per compaction chunk (RenderConfig::block):
+// f(std::integral_constant<int, BS>) for the chunk's BS.
+template <class F>
+static void with_chunk(int chunk, F&& f) {
+    switch (chunk) {
+        case 64: f(std::integral_constant<int, 64>{}); break;
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        default: f(std::integral_constant<int, 256>{}); break;
     }
+}
+
+void Renderer::launchBounce(const KParams& k, hipStream_t st, bool first, dim3 grid, int iter, int b, int accel) {
+    with_chunk(k.chunk, [&](auto bs) {
+        constexpr int BS = decltype(bs)::value;
+        if (first) launch_bounce_bs<true, BS>(accel, grid, st, k, iter, b);
+        else launch_bounce_bs<false, BS>(accel, grid, st, k, iter, b);
+    });
 }
 
 // Bounce 0 of a masked iteration (renderLoopMasked): tile_mask is the device copy of the mask.
 void Renderer::launchBounceMasked(const KParams& k, hipStream_t st, dim3 grid, int iter, const unsigned char* tile_mask) {
     const int tx = noiseTilesX();
-    switch (k.chunk) {
-        case 64: hipLaunchKernelGGL(k_bounce_masked<64>, grid, dim3(64), 0, st, k, iter, tile_mask, tx); break;
-        case 128: hipLaunchKernelGGL(k_bounce_masked<128>, grid, dim3(128), 0, st, k, iter, tile_mask, tx); break;
-        default: hipLaunchKernelGGL(k_bounce_masked<256>, grid, dim3(256), 0, st, k, iter, tile_mask, tx); break;
-    }
+    with_chunk(k.chunk, [&](auto bs) {
+        constexpr int BS = decltype(bs)::value;
+        hipLaunchKernelGGL(k_bounce_masked<BS>, grid, dim3(BS), 0, st, k, iter, tile_mask, tx);
+    });
 }
 
 // Bounce 0 of a jittered iteration: one workgroup per compaction chunk of launched pixels
@@ -3786,20 +3646,11 @@ void Renderer::launchGenJitter(const KParams& k, hipStream_t st, int iter, const
     const int tx = noiseTilesX();
     const float w = jitter_width;
     const dim3 grid((unsigned)((k.npix + k.chunk - 1) / k.chunk));
-    switch (k.chunk) {
-        case 64:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<64, true>), grid, dim3(64), 0, st, k, iter, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_jitter<64, false>), grid, dim3(64), 0, st, k, iter, w, tile_mask, tx);
-            break;
-        case 128:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<128, true>), grid, dim3(128), 0, st, k, iter, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_jitter<128, false>), grid, dim3(128), 0, st, k, iter, w, tile_mask, tx);
-            break;
-        default:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<256, true>), grid, dim3(256), 0, st, k, iter, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_jitter<256, false>), grid, dim3(256), 0, st, k, iter, w, tile_mask, tx);
-            break;
-    }
+    with_chunk(k.chunk, [&](auto bs) {
+        constexpr int BS = decltype(bs)::value;
+        if (tile_mask) hipLaunchKernelGGL((k_gen_jitter<BS, true>), grid, dim3(BS), 0, st, k, iter, w, tile_mask, tx);
+        else hipLaunchKernelGGL((k_gen_jitter<BS, false>), grid, dim3(BS), 0, st, k, iter, w, tile_mask, tx);
+    });
 }
 
 // k_gen_jitter's launch for the free camera: the jitter state rides along as an argument
@@ -3808,20 +3659,11 @@ void Renderer::launchGenCamera(const KParams& k, hipStream_t st, int iter, const
     const int jit = jitter_on ? 1 : 0;
     const float w = jitter_width;
     const dim3 grid((unsigned)((k.npix + k.chunk - 1) / k.chunk));
-    switch (k.chunk) {
-        case 64:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<64, true>), grid, dim3(64), 0, st, k, iter, jit, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_camera<64, false>), grid, dim3(64), 0, st, k, iter, jit, w, tile_mask, tx);
-            break;
-        case 128:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<128, true>), grid, dim3(128), 0, st, k, iter, jit, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_camera<128, false>), grid, dim3(128), 0, st, k, iter, jit, w, tile_mask, tx);
-            break;
-        default:
-            if (tile_mask) hipLaunchKernelGGL((k_gen_camera<256, true>), grid, dim3(256), 0, st, k, iter, jit, w, tile_mask, tx);
-            else hipLaunchKernelGGL((k_gen_camera<256, false>), grid, dim3(256), 0, st, k, iter, jit, w, tile_mask, tx);
-            break;
-    }
+    with_chunk(k.chunk, [&](auto bs) {
+        constexpr int BS = decltype(bs)::value;
+        if (tile_mask) hipLaunchKernelGGL((k_gen_camera<BS, true>), grid, dim3(BS), 0, st, k, iter, jit, w, tile_mask, tx);
+        else hipLaunchKernelGGL((k_gen_camera<BS, false>), grid, dim3(BS), 0, st, k, iter, jit, w, tile_mask, tx);
+    });
 }
 
 int Renderer::setCamera(const CameraRec* cam) {
@@ -3912,7 +3754,7 @@ int Renderer::enqueueSortTrace(const KParams& k, hipStream_t st, int b, bool pal
     if (k.order) {
         if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
         const dim3 sg((unsigned)((k.nblocks * (size_t)k.chunk + kSortWG * kSortPer - 1) / (kSortWG * kSortPer)));
-        if (host_rays || !PT_WRITER_KEYS) hipLaunchKernelGGL(k_sort_hist<true>, sg, dim3(kSortWG), 0, st, k, b);
+        if (host_rays) hipLaunchKernelGGL(k_sort_hist<true>, sg, dim3(kSortWG), 0, st, k, b);
         else hipLaunchKernelGGL(k_sort_hist<false>, sg, dim3(kSortWG), 0, st, k, b);
         hipLaunchKernelGGL(k_sort_prefix, dim3(1), dim3(kSortWG), 0, st, k);
         hipLaunchKernelGGL(k_sort_scatter, sg, dim3(kSortWG), 0, st, k, b);

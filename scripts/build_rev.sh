@@ -11,7 +11,7 @@ git archive "$REV" pathtracerap_amd/csrc include | tar -x -C $T
 cd $T/pathtracerap_amd && mkdir -p o
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-result -Wno-unused-value -Wno-pass-failed $D"
 for s in scene bvh capi; do /opt/rocm/bin/hipcc $F -x hip -c csrc/$s.cpp -o o/$s.o & done
-/opt/rocm/bin/hipcc $F -c csrc/renderer.hip -o o/renderer.o
+for s in csrc/*.hip; do /opt/rocm/bin/hipcc $F -c $s -o o/$(basename $s .hip).o & done   # renderer, film (newer revisions)
 wait
 /opt/rocm/bin/hipcc $F -shared -o ../../lib_$NAME.so o/*.o
 cd ../../.. && rm -rf $T
