@@ -143,6 +143,79 @@ int pt_scene_add_model(pt_scene *s, int mesh, const float scale[3], const float 
 int pt_scene_set_model_smooth(pt_scene *s, int model, int on);
 /* The flag of one model: 0 or 1; negative: error ("pt_scene_model_smooth: bad model index"). */
 int pt_scene_model_smooth(const pt_scene *s, int model);
+/* ---- Albedo textures: per-vertex uvs and a bilinear lookup at the hit, per model (added within
+ * ABI 9: new functions only; pt_render_config, pt_scene_add_mesh, pt_scene_add_model and
+ * PT_ABI_VERSION are unchanged.  No counterpart in the reference, whose Primitive.h declares a uv
+ * and never reads it).  Off by default: a scene with no textured model allocates, launches and
+ * computes exactly what it did. ----
+ * pt_scene_set_mesh_uv stores nv*2 floats (u, v per vertex) for the mesh's vertices, in
+ * pt_scene_add_mesh's vertex order; `built`, the grid and the BLAS are left alone.  Refused:
+ * "setMeshUv: bad mesh index", "setMeshUv: nv is not the mesh's vertex count", "setMeshUv:
+ * non-finite uv".  pt_scene_export_uv writes nv_total*2 floats, (0, 0) for the vertices of a mesh
+ * without uv (uv_out may be null), and returns the vertex count.  pt_scene_mesh_has_uv: 0 or 1.
+ * Where uvs come from otherwise: pt_scene_load_obj reads `vt u v` and the middle index of the
+ * v/vt/vn and v/vt corner forms, with negative indices as for v, and stores (u, 1.0f - v), which
+ * is what the reference's one import flag, aiProcess_FlipUVs, does.  A corner without vt gets
+ * (0, 0), and the mesh has uv when any corner named one.  A bad vt index is refused like a bad vn
+ * index.  One exception: a face that comes before the file's first vt line has its middle
+ * indices ignored, as the loader always ignored them.  A generated SPHERE gives vertex (j, i) the uv ((float)((double)i / 48),
+ * (float)((double)j / 24)); a generated BOX gives each face's four corners (0,0), (1,0), (1,1),
+ * (0,1) in the order it emits them.
+ * pt_scene_add_texture copies w*h*3 floats, texel (row y, column x) at rgb[3*(y*w + x)], and
+ * returns the texture's index.  Refused: "addTexture: width and height must be in [1,4096]",
+ * "addTexture: non-finite texel".  pt_scene_texture reads one back (w, h, rgb_out may be null);
+ * pt_scene_texture_count is the number of textures.
+ * pt_scene_set_model_texture binds texture (-1: none) to model (-1: every model added so far),
+ * before or after pt_scene_build.  Refused: "setModelTexture: bad model index", "setModelTexture:
+ * bad texture index", "setModelTexture: mesh has no uv".  pt_scene_model_texture returns the
+ * binding, -1 for none; -2: error ("pt_scene_model_texture: bad model index").
+ * pt_renderer_allocate_on_gpu snapshots the bindings: a change made afterwards applies to the next
+ * allocation.  When some model is textured the allocation also uploads every texture's texels
+ * (16 bytes each), the shading table of pt_scene_set_model_smooth with the vertex uvs in its
+ * spare lanes, and a 16-byte-per-pixel plane of the primary hits' albedos.
+ * Definition.  The albedo mc of a hit of the world ray (o, d) at world distance dist on scene
+ * triangle T of model M, when M has texture X of w x h texels; float32 IEEE in exactly this
+ * order, no fused multiply-add.  b0, b1, b2 are those of pt_scene_set_model_smooth's definition
+ * above, bit for bit (the same ip, pm, q, den, the same two clamps, b0 = (1.0f - b1) - b2);
+ * uv0, uv1, uv2 the triangle's three stored vertex uvs:
+ *   uv_k = (uv0_k*b0 + uv1_k*b1) + uv2_k*b2                 k = u, v
+ *   per axis (a = uv_u with n = w gives x0, x1, tx;  a = uv_v with n = h gives y0, y1, ty):
+ *     fr = a - floorf(a)                                    repeat wrap
+ *     f  = fr * (float)n - 0.5f
+ *     f  = fminf(fmaxf(f, -0.5f), (float)n - 0.5f)          a NaN gives way: f = -0.5
+ *     fl = floorf(f);  t = f - fl
+ *     i0 = (int)fl;  if (i0 < 0) i0 += n;  i1 = i0 + 1;  if (i1 >= n) i1 -= n
+ *   per channel:
+ *     top = X[y0][x0] + (X[y0][x1] - X[y0][x0]) * tx
+ *     bot = X[y1][x0] + (X[y1][x1] - X[y1][x0]) * tx
+ *     v   = top + (bot - top) * ty
+ *   mc  = color_M * v                                       the model's own colour tints the texture
+ * mc takes the place of the model colour wherever the shading reads it: the r.c = r.c * mc of
+ * DIFFUSE, METAL, COAT, EMISSIVE and REFLECTIVE hits with bounces left (a textured EMISSIVE
+ * model is a textured light).  No random draw, slot, compaction order or segment count changes.
+ * mc is a function of (o, d, dist, model, triangle) alone, so every path that shades a hit gets
+ * the same bits.  No load leaves the texture: fl lies in [-1, n-1], so i0 and i1 lie in [0, n-1]
+ * for every float input, a NaN and fr*n rounding up to n included.
+ * Limits.  No mip levels and no ray differentials: minification aliases, and pixel jitter is the
+ * remedy.  Texels are linear values; a PPM's bytes are not gamma-decoded.  The denoiser does not
+ * demodulate albedo: inside one model only its luminance term stops at texture detail, so a
+ * strong filter blurs the pattern; pt_renderer_primary_albedo is the input a later
+ * demodulation would need.
+ * Config grammar: a block TEXTURE / <name> / CHECKER / [r,g,b] / [r,g,b] / N makes an N x N
+ * texture, 1 <= N <= 4096, whose texel (y, x) is the first colour when x + y is even and the
+ * second otherwise; TEXTURE / <name> / PPM / <path> loads a binary P6 file with maxval <= 255
+ * (a texel is (float)byte / (float)maxval; the path resolves like an OBJ path; a malformed file
+ * is refused with the path in the message).  TEXTURE blocks are collected first, like material
+ * blocks.  MESH, SPHERE and BOX blocks take the attribute texture:<name> (an unknown name is
+ * refused: "unknown texture ..."). */
+int pt_scene_set_mesh_uv(pt_scene *s, int mesh, const float *uv, int nv);
+int pt_scene_export_uv(const pt_scene *s, float *uv_out);              /* -> vertex count */
+int pt_scene_mesh_has_uv(const pt_scene *s, int mesh);
+int pt_scene_add_texture(pt_scene *s, int w, int h, const float *rgb); /* -> texture index */
+int pt_scene_texture_count(const pt_scene *s);
+int pt_scene_texture(const pt_scene *s, int texture, int *w, int *h, float *rgb_out);
+int pt_scene_set_model_texture(pt_scene *s, int model, int texture);
+int pt_scene_model_texture(const pt_scene *s, int model);
 /* with_bvh: also build the per-mesh BLAS (needed by PT_ACCEL_GRID_FAST and PT_ACCEL_BVH;
  * pt_renderer_allocate_on_gpu adds it on demand to a scene built without it). */
 int pt_scene_build(pt_scene *s, const int grid[3], int with_bvh);
@@ -581,6 +654,18 @@ int pt_renderer_environment(pt_renderer *r, pt_environment *out, float *texels_o
 /* Test hook: the lookup above, without the final c * ..., on the device for `count` directions
  * dirs[3*count] -> rgb_out[3*count].  Needs allocate_on_gpu and an environment. */
 int pt_renderer_env_lookup(pt_renderer *r, int count, const float *dirs, float *rgb_out);
+/* The albedo mc (pt_scene_set_model_texture's definition) of each pixel's cached primary hit:
+ * rgb_out[3*width*height], (0, 0, 0) for a miss and for a pixel tail_drop leaves out.  Works
+ * without textures too, where it is the hit model's colour.  Needs allocate_on_gpu.  No
+ * counterpart in the reference. */
+int pt_renderer_primary_albedo(pt_renderer *r, float *rgb_out);
+/* Test hook: that definition evaluated on the device for n caller-given hits: orig[3n], dir[3n],
+ * and the dist[n], model[n], tri[n] pt_renderer_trace_rays returns -> rgb_out[3n].  An untextured
+ * model gives its colour, model < 0 gives (0, 0, 0).  Refused before any launch: "hit_albedo:
+ * model index out of range", "hit_albedo: triangle index out of range".  No counterpart in the
+ * reference. */
+int pt_renderer_hit_albedo(pt_renderer *r, int n, const float *orig, const float *dir, const float *dist,
+                           const int *model, const int *tri, float *rgb_out);
 /* Fills an n x n octahedral map with a sky (host only): texels_out[3*(y*n + x) + k], k = r, g, b.
  * Texel (y, x)'s centre is decoded to a direction, float32 in exactly this order:
  *   px = (((float)x + 0.5f) / (float)n) * 2.0f - 1.0f;  py likewise from y

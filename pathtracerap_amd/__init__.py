@@ -104,6 +104,14 @@ EXPORTS = [
     ("pt_scene_add_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
     ("pt_scene_set_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     ("pt_scene_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("pt_scene_set_mesh_uv", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, ctypes.c_int]),
+    ("pt_scene_export_uv", ctypes.c_int, [ctypes.c_void_p, _P_F]),
+    ("pt_scene_mesh_has_uv", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("pt_scene_add_texture", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _P_F]),
+    ("pt_scene_texture_count", ctypes.c_int, [ctypes.c_void_p]),
+    ("pt_scene_texture", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_I, _P_I, _P_F]),
+    ("pt_scene_set_model_texture", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    ("pt_scene_model_texture", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("pt_scene_build", ctypes.c_int, [ctypes.c_void_p, _P_I, ctypes.c_int]),
     ("pt_scene_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
     ("pt_scene_export", ctypes.c_int, [ctypes.c_void_p, _P_F, _P_F, _P_I, _P_I, _P_F, _P_I, _P_F, _P_F,
@@ -162,6 +170,8 @@ EXPORTS = [
     ("pt_renderer_set_environment", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Environment)]),
     ("pt_renderer_environment", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Environment), _P_F]),
     ("pt_renderer_env_lookup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F]),
+    ("pt_renderer_primary_albedo", ctypes.c_int, [ctypes.c_void_p, _P_F]),
+    ("pt_renderer_hit_albedo", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, _P_I, _P_I, _P_F]),
     ("pt_environment_sky", ctypes.c_int, [_P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
@@ -438,14 +448,61 @@ class Scene:
         tris = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
         return _err(lib().pt_scene_add_mesh(self._h, _fp(pos), _fp(nrm), len(pos), _ip(tris), len(tris)), "addMesh")
 
-    def addModel(self, mesh: int, scale, rot_deg, translate, material, color, smooth: bool = False) -> int:
+    def addModel(self, mesh: int, scale, rot_deg, translate, material, color, smooth: bool = False,
+                 texture: int | None = None) -> int:
         mt = MATERIALS[material] if isinstance(material, str) else int(material)
         s = np.array(scale, np.float32); r = np.array(rot_deg, np.float32)
         t = np.array(translate, np.float32); c = np.array(color, np.float32)
         m = _err(lib().pt_scene_add_model(self._h, int(mesh), _fp(s), _fp(r), _fp(t), mt, _fp(c)), "addModel")
         if smooth:
             self.set_smooth(m)
+        if texture is not None:
+            self.set_texture(m, texture)
         return m
+
+    def set_mesh_uv(self, mesh: int, uv) -> None:
+        """Per-vertex (u, v) of ``mesh``, one row per vertex in ``addMesh``'s order
+        (pt_scene_set_mesh_uv).  The grid and the BLAS are not touched."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        _err(lib().pt_scene_set_mesh_uv(self._h, int(mesh), _fp(uv), len(uv)), "set_mesh_uv")
+
+    def mesh_has_uv(self, mesh: int) -> bool:
+        return _err(lib().pt_scene_mesh_has_uv(self._h, int(mesh)), "mesh_has_uv") != 0
+
+    def add_texture(self, rgb) -> int:
+        """An (h, w, 3) array of linear RGB texels -> the texture's index (pt_scene_add_texture)."""
+        t = np.ascontiguousarray(rgb, np.float32)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise PathTracerError("add_texture: texels must have shape (h, w, 3)")
+        return _err(lib().pt_scene_add_texture(self._h, t.shape[1], t.shape[0], _fp(t)), "add_texture")
+
+    def set_texture(self, model: int | None = None, texture: int | None = None) -> None:
+        """Bind ``texture`` (None: no texture) as the albedo of ``model`` (None: every model added
+        so far) (pt_scene_set_model_texture).  Before or after ``build``; a renderer reads the
+        bindings in ``allocateOnGPU``."""
+        _err(lib().pt_scene_set_model_texture(self._h, -1 if model is None else int(model),
+                                              -1 if texture is None else int(texture)), "set_texture")
+
+    def model_textures(self) -> np.ndarray:
+        """The texture index of every model, -1 for none (pt_scene_model_texture)."""
+        out = []
+        for i in range(self.counts()["nmodel"]):
+            t = lib().pt_scene_model_texture(self._h, i)
+            if t < -1:
+                _err(-1, "model_textures")
+            out.append(t)
+        return np.array(out, np.int32)
+
+    def textures(self) -> list:
+        """Every texture as an (h, w, 3) float32 array (pt_scene_texture)."""
+        out = []
+        for i in range(_err(lib().pt_scene_texture_count(self._h), "textures")):
+            w = ctypes.c_int(); h = ctypes.c_int()
+            _err(lib().pt_scene_texture(self._h, i, ctypes.byref(w), ctypes.byref(h), None), "textures")
+            t = np.zeros((h.value, w.value, 3), np.float32)
+            _err(lib().pt_scene_texture(self._h, i, None, None, _fp(t)), "textures")
+            out.append(t)
+        return out
 
     def set_smooth(self, model: int | None = None, on: bool = True) -> None:
         """Shade ``model`` (None: every model added so far) with the interpolated vertex normals
@@ -487,6 +544,8 @@ class Scene:
             _ip(a["model_ints"]), _fp(a["model_m2w"]), _fp(a["model_w2m"]), _fp(a["model_color"]),
             _ip(a["grid_ints"]), _fp(a["grid_vw"]), _ip(a["vox"]), _ip(a["per_voxel"])), "export")
         a["per_voxel"] = a["per_voxel"][:n["npv"]]
+        a["uv"] = np.zeros((n["nv"], 2), np.float32)
+        _err(lib().pt_scene_export_uv(self._h, _fp(a["uv"])), "export uv")
         return a
 
 
@@ -618,6 +677,27 @@ class Renderer:
         d = np.zeros(n, np.float32); nn = np.zeros((n, 3), np.float32); m = np.zeros(n, np.int32)
         _err(lib().pt_renderer_primary_hits(self._h, _fp(d), _fp(nn), _ip(m)), "primary_hits")
         return d, nn, m
+
+    def primary_albedo(self) -> np.ndarray:
+        """The albedo of each pixel's cached primary hit, (W*H, 3): the model colour times its
+        texture's value at the hit; zero for a miss (pt_renderer_primary_albedo)."""
+        out = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
+        _err(lib().pt_renderer_primary_albedo(self._h, _fp(out)), "primary_albedo")
+        return out
+
+    def hit_albedo(self, orig, dirs, dist, model, tri) -> np.ndarray:
+        """Test hook: the albedo definition on the device for caller-given hits, the
+        ``(dist, model, tri)`` of ``trace_rays`` (pt_renderer_hit_albedo) -> (n, 3)."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        dd = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(dist, np.float32).reshape(-1)
+        m = np.ascontiguousarray(model, np.int32).reshape(-1)
+        tr = np.ascontiguousarray(tri, np.int32).reshape(-1)
+        if not (len(o) == len(dd) == len(t) == len(m) == len(tr)):
+            raise PathTracerError("hit_albedo: arrays differ in length")
+        out = np.zeros((len(o), 3), np.float32)
+        _err(lib().pt_renderer_hit_albedo(self._h, len(o), _fp(o), _fp(dd), _fp(t), _ip(m), _ip(tr), _fp(out)), "hit_albedo")
+        return out
 
     def intersect_rays(self, orig, dirs):
         o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)

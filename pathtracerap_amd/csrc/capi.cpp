@@ -129,6 +129,54 @@ int pt_scene_model_smooth(const pt_scene* s, int model) {
     return rc < 0 ? set_err("pt_scene_model_smooth: bad model index") : rc;
 }
 
+int pt_scene_set_mesh_uv(pt_scene* s, int mesh, const float* uv, int nv) {
+    if (!uv) return set_err("pt_scene_set_mesh_uv: null argument");
+    SCENE_CALL(s->s.setMeshUv(mesh, uv, nv));
+}
+
+int pt_scene_export_uv(const pt_scene* s, float* uv_out) {
+    if (!s) return set_err("null scene");
+    const pt::Scene& S = s->s;
+    if (uv_out)
+        for (size_t i = 0; i < S.vertices.size() * 2; i++) uv_out[i] = i < S.vertex_uv.size() ? S.vertex_uv[i] : 0.0f;
+    return (int)S.vertices.size();
+}
+
+int pt_scene_mesh_has_uv(const pt_scene* s, int mesh) {
+    if (!s) return set_err("null scene");
+    const int rc = s->s.meshHasUv(mesh);
+    return rc < 0 ? set_err("pt_scene_mesh_has_uv: bad mesh index") : rc;
+}
+
+int pt_scene_add_texture(pt_scene* s, int w, int h, const float* rgb) {
+    if (!rgb) return set_err("pt_scene_add_texture: null argument");
+    SCENE_CALL(s->s.addTexture(w, h, rgb));
+}
+
+int pt_scene_set_model_texture(pt_scene* s, int model, int texture) { SCENE_CALL(s->s.setModelTexture(model, texture)); }
+
+int pt_scene_model_texture(const pt_scene* s, int model) {
+    if (!s) return set_err("null scene");
+    int t = -1;
+    if (s->s.modelTexture(model, &t) < 0) { set_err("pt_scene_model_texture: bad model index"); return -2; }
+    return t;
+}
+
+int pt_scene_texture_count(const pt_scene* s) {
+    if (!s) return set_err("null scene");
+    return (int)s->s.textures.size();
+}
+
+int pt_scene_texture(const pt_scene* s, int texture, int* w, int* h, float* rgb_out) {
+    if (!s) return set_err("null scene");
+    if (texture < 0 || texture >= (int)s->s.textures.size()) return set_err("pt_scene_texture: bad texture index");
+    const pt::Texture& t = s->s.textures[texture];
+    if (w) *w = t.w;
+    if (h) *h = t.h;
+    if (rgb_out) std::memcpy(rgb_out, t.rgb.data(), t.rgb.size() * sizeof(float));
+    return 0;
+}
+
 int pt_scene_build(pt_scene* s, const int grid[3], int with_bvh) {
     const int def[3] = {25, 25, 25};
     SCENE_CALL(s->s.build(grid ? grid : def, with_bvh != 0));
@@ -402,6 +450,18 @@ int pt_renderer_environment(pt_renderer* r, pt_environment* out, float* texels_o
 }
 int pt_renderer_env_lookup(pt_renderer* r, int count, const float* dirs, float* rgb_out) {
     R_CALL(r->r->envLookup(count, dirs, rgb_out));
+}
+
+int pt_renderer_primary_albedo(pt_renderer* r, float* rgb_out) {
+    if (!r || !rgb_out) return set_err("pt_renderer_primary_albedo: null argument");
+    R_CALL(r->r->primaryAlbedo(rgb_out));
+}
+
+int pt_renderer_hit_albedo(pt_renderer* r, int n, const float* orig, const float* dir, const float* dist,
+                           const int* model, const int* tri, float* rgb_out) {
+    if (!r || (n > 0 && (!orig || !dir || !dist || !model || !tri || !rgb_out)))
+        return set_err("pt_renderer_hit_albedo: null argument");
+    R_CALL(r->r->hitAlbedo(n, orig, dir, dist, model, tri, rgb_out));
 }
 
 int pt_environment_sky(const float zenith[3], const float horizon[3], const float ground[3], int n, float* texels_out) {

@@ -59,17 +59,28 @@ struct ModelShade {
     float color[3];       // Material::color
     int mat_type;         // Material::MaterialType
     int smooth;           // 1: the hit normal interpolates the vertex normals (pt_scene_set_model_smooth)
-    int pad[3];
+    int texture;          // the albedo texture's index (pt_scene_set_model_texture), -1: none; read only
+                          // when the renderer holds textures (KParams::tex)
+    int pad[2];
 };
 static_assert(sizeof(ModelShade) == 32, "ModelShade layout");
 
 // One triangle of the shading table (KParams::smooth): what the smooth hit normal reads, one
-// 96-byte record -- tri_geom's v0, e1, e2 and the three stored vertex normals (w lanes unused).
+// 96-byte record -- tri_geom's v0, e1, e2 and the three stored vertex normals.  The six w lanes
+// carry the triangle's vertex uvs in record order: (v0.w, e1.w) = uv0, (e2.w, n0.w) = uv1,
+// (n1.w, n2.w) = uv2 (zero in a scene without a textured model).
 struct TriShade {
     float v0[4], e1[4], e2[4];
     float n0[4], n1[4], n2[4];
 };
 static_assert(sizeof(TriShade) == 96, "TriShade layout");
+
+// One model's texture in KParams::tex: its first texel's index in the buffer (in float4 units)
+// and its size.  Whether the model has a texture is ModelShade::texture's to say; a model
+// without one has a record of one texel, never used.  The buffer starts with one record per
+// model, 16 bytes each like a texel.
+struct TexRec { int offset, w, h, pad; };
+static_assert(sizeof(TexRec) == 16, "TexRec layout");
 
 // 2-wide BVH node: both children's boxes in one 64-byte line.
 // link/count: count == 0 -> link is a child node index; count > 0 -> link is

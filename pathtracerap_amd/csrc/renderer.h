@@ -127,6 +127,13 @@ struct KParams {
     const TriShade* smooth;             // the shading table (one record per scene triangle) of a scene with a
                                         // smooth model; null: every hit normal is the flat one and nothing
                                         // more is loaded.  Static per allocation.  Last, for the same reason
+    const float4* tex;                  // the albedo textures of a scene with a textured model: one TexRec per
+                                        // model, then every texture's texels, a float4 each (rgb, w unused);
+                                        // null: a hit's albedo is its model's colour and nothing more is loaded.
+                                        // With it, `smooth` is set too (the table carries the vertex uvs).
+                                        // Static per allocation.  Last, for the same reason
+    float4* cache_albedo;               // with tex: the albedo of each pixel's cached primary hit (k_primary),
+                                        // which bounce 0 multiplies by instead of ModelShade::color; else null
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
@@ -221,6 +228,10 @@ public:
     // 1: set, 0: none.  out: n, scale and rotation (texels_rgb null); texels_out: n * n * 3 floats
     int environment(pt_environment* out, float* texels_out) const;
     int envLookup(int count, const float* dirs, float* rgb_out);     // test hook: env_radiance of each direction
+    int primaryAlbedo(float* rgb_out);   // W*H*3: the albedo of each pixel's cached primary hit, 0 for a miss
+    // test hook: the albedo definition evaluated on the device for caller-given hits
+    int hitAlbedo(int n, const float* orig, const float* dir, const float* dist, const int* model, const int* tri,
+                  float* rgb_out);
 
     RenderConfig cfg;
     std::string last_error;
@@ -266,6 +277,9 @@ private:
     bool stream_set = false;
     bool allocated = false;
     bool cache_valid = false;        // is_first_intersection_cached (Renderer.cpp:580)
+    int alloc_ntris = 0;             // the allocation's scene triangle count (hitAlbedo's range check)
+    std::vector<float> alloc_color;  // the allocation's model colours, 3 per model (primaryAlbedo without textures)
+    size_t tex_bytes = 0;            // bytes the allocation uploaded for textures (texels, records, shading table)
     bool external_image = false;
     float* ext_image = nullptr;
     bool moments_on = false;         // enableMoments: every pipeline has a contribution buffer, k_merge_m2 merges

@@ -1118,8 +1118,10 @@ __device__ __forceinline__ TriShadeRec load_tri_shade(const TriShade* tab, int t
     T.v0 = q[0]; T.e1 = q[1]; T.e2 = q[2]; T.n0 = q[3]; T.n1 = q[4]; T.n2 = q[5];
     return T;
 }
-__device__ __forceinline__ f3 smooth_normal(const float* w2m, const float* nm, const TriShadeRec& T, f3 o, f3 d,
-                                            float dist, f3 g) {
+// The clamped barycentrics of the hit point on its triangle, the one computation the smooth
+// normal and the albedo texture share.
+struct Bary { float b0, b1, b2; };
+__device__ __forceinline__ Bary hit_bary(const float* w2m, const TriShadeRec& T, f3 o, f3 d, float dist) {
     const f3 dir = normalize(d);
     const f3 ip = o + dir * dist;
     const f3 pm = xform12(w2m, ip, 1.0f);
@@ -1131,7 +1133,12 @@ __device__ __forceinline__ f3 smooth_normal(const float* w2m, const float* nm, c
     float b2 = (d11 * q2 - d12 * q1) / den;
     b1 = fminf(fmaxf(b1, 0.0f), 1.0f);              // fmaxf / fminf drop a NaN (den = 0)
     b2 = fminf(fmaxf(b2, 0.0f), 1.0f - b1);
-    const float b0 = (1.0f - b1) - b2;
+    Bary B;
+    B.b0 = (1.0f - b1) - b2; B.b1 = b1; B.b2 = b2;
+    return B;
+}
+__device__ __forceinline__ f3 smooth_normal(const float* nm, const TriShadeRec& T, const Bary& B, f3 g) {
+    const float b0 = B.b0, b1 = B.b1, b2 = B.b2;
     const f3 m = mk3((T.n0.x * b0 + T.n1.x * b1) + T.n2.x * b2, (T.n0.y * b0 + T.n1.y * b1) + T.n2.y * b2,
                      (T.n0.z * b0 + T.n1.z * b1) + T.n2.z * b2);
     const f3 s = normalize(xform_normal9(nm, m));
@@ -1146,7 +1153,63 @@ __device__ __forceinline__ f3 smooth_normal(const float* w2m, const float* nm, c
 __device__ __forceinline__ f3 shading_normal(const KParams& p, f3 o, f3 d, float dist, int model, int tri, f3 g) {
     if (!p.smooth || model < 0 || tri < 0 || !p.shade[model].smooth) return g;
     const ModelRec& M = p.models[model];
-    return smooth_normal(M.w2m, M.nm, load_tri_shade(p.smooth, tri), o, d, dist, g);
+    const TriShadeRec T = load_tri_shade(p.smooth, tri);
+    return smooth_normal(M.nm, T, hit_bary(M.w2m, T, o, d, dist), g);
+}
+
+// The albedo texture lookup (include/pathtracer_amd.h, pt_scene_set_model_texture, states it).
+// One axis: coordinate a on n texels -> the two texel indices, both in [0, n-1] for every float
+// a (a NaN or an infinity gives fr = NaN, which the clamp turns into f = -0.5), and the weight t.
+__device__ __forceinline__ void tex_axis(float a, int n, int& i0, int& i1, float& t) {
+    const float fr = a - floorf(a);
+    float f = fr * (float)n - 0.5f;
+    f = fminf(fmaxf(f, -0.5f), (float)n - 0.5f);
+    const float fl = floorf(f);
+    t = f - fl;
+    i0 = (int)fl;
+    if (i0 < 0) i0 += n;
+    i1 = i0 + 1;
+    if (i1 >= n) i1 -= n;                   // f in [-0.5, n - 0.5], so fl in [-1, n - 1]: both indices in [0, n - 1]
+}
+// The interpolated uv of the hit: the record's w lanes are (uv0.u, uv0.v, uv1.u, uv1.v, uv2.u, uv2.v).
+__device__ __forceinline__ void hit_uv(const TriShadeRec& T, const Bary& B, float& u, float& v) {
+    u = (T.v0.w * B.b0 + T.e2.w * B.b1) + T.n1.w * B.b2;
+    v = (T.e1.w * B.b0 + T.n0.w * B.b1) + T.n2.w * B.b2;
+}
+// The four taps' addresses of texture record R at (u, v), and the weights.
+struct TexTaps { int a00, a01, a10, a11; float tx, ty; };
+__device__ __forceinline__ TexTaps tex_taps(int4 R, float u, float v) {
+    int x0, x1, y0, y1;
+    TexTaps t;
+    tex_axis(u, R.y, x0, x1, t.tx);
+    tex_axis(v, R.z, y0, y1, t.ty);
+    t.a00 = R.x + y0 * R.y + x0; t.a01 = R.x + y0 * R.y + x1;
+    t.a10 = R.x + y1 * R.y + x0; t.a11 = R.x + y1 * R.y + x1;
+    return t;
+}
+__device__ __forceinline__ f3 tex_blend(float4 c00, float4 c01, float4 c10, float4 c11, float tx, float ty, f3 color) {
+    const f3 top = mk3(c00.x + (c01.x - c00.x) * tx, c00.y + (c01.y - c00.y) * tx, c00.z + (c01.z - c00.z) * tx);
+    const f3 bot = mk3(c10.x + (c11.x - c10.x) * tx, c10.y + (c11.y - c10.y) * tx, c10.z + (c11.z - c10.z) * tx);
+    const f3 v = mk3(top.x + (bot.x - top.x) * ty, top.y + (bot.y - top.y) * ty, top.z + (bot.z - top.z) * ty);
+    return color * v;
+}
+__device__ __forceinline__ f3 tex_albedo(const float4* tex, int model, const TriShadeRec& T, const Bary& B, f3 color) {
+    const int4 R = reinterpret_cast<const int4*>(tex)[model];      // the model's TexRec
+    float u, v;
+    hit_uv(T, B, u, v);
+    const TexTaps t = tex_taps(R, u, v);
+    return tex_blend(tex[t.a00], tex[t.a01], tex[t.a10], tex[t.a11], t.tx, t.ty, color);
+}
+// The albedo of a hit: the model's colour, times its texture's value on a textured model.
+// p.tex is a kernel argument (wave-uniform): a scene without a textured model loads only the
+// colour.  model >= 0.  The slot-map form of k_bounce<rest, hitbuf, BS, true, true> restates
+// this selection with its loads hoisted: an edit here belongs there too.
+__device__ __forceinline__ f3 hit_albedo(const KParams& p, f3 o, f3 d, float dist, int model, int tri) {
+    const ModelShade& S = p.shade[model];
+    const f3 color = mk3(S.color[0], S.color[1], S.color[2]);
+    if (!p.tex || tri < 0 || S.texture < 0) return color;
+    const TriShadeRec T = load_tri_shade(p.smooth, tri);
+    return tex_albedo(p.tex, model, T, hit_bary(p.models[model].w2m, T, o, d, dist), color);
 }
 
 // Hit record of the split trace -> shade path (p.hit4 / p.hitm, slot j):
@@ -1204,14 +1267,20 @@ __device__ void intersect_scene_g(const KParams& p, f3 orig, f3 dir, int* stack,
     }
 }
 
+// gtri: the hit triangle (what hit_albedo needs beside the Hit).
 template <int ACCEL, int STRIDE>
-__device__ Hit intersect_scene(const KParams& p, f3 orig, f3 dir, int* stack, int4* hs) {
+__device__ __forceinline__ Hit intersect_scene(const KParams& p, f3 orig, f3 dir, int* stack, int4* hs, int& gtri) {
     float gdist;
-    int gmodel, gtri;
+    int gmodel;
     intersect_scene_g<ACCEL, STRIDE>(p, orig, dir, stack, hs, gdist, gmodel, gtri);
     Hit h = make_hit(p, gdist, gmodel, gtri);
     if (p.smooth) h.n = shading_normal(p, orig, dir, h.dist, h.model, gtri, h.n);
     return h;
+}
+template <int ACCEL, int STRIDE>
+__device__ Hit intersect_scene(const KParams& p, f3 orig, f3 dir, int* stack, int4* hs) {
+    int gtri;
+    return intersect_scene<ACCEL, STRIDE>(p, orig, dir, stack, hs, gtri);
 }
 
 // The free camera's point of pixel coordinates (fx, fy): (p0 + fx*du) + fy*dv per coordinate,
@@ -1275,13 +1344,27 @@ __device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, i
     r.bounces--;
 }
 
-__device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& h, int iter, int slot) {
+// tri: the hit triangle, for the albedo of a textured scene (p.tex, a kernel argument:
+// wave-uniform); kTriCached: the hit is pixel `slot`'s cached primary hit, whose albedo k_primary
+// left in p.cache_albedo.  Without textures the albedo is the model's colour, as it was.
+// MAYTEX = false: a kernel never launched for a textured scene, which compiles none of it.
+constexpr int kTriCached = -2;
+template <bool MAYTEX = true>
+__device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& h, int iter, int slot, int tri) {
     int mt = 0;
     f3 mc = mk3(0, 0, 0);
     if (h.dist < kFMax && r.bounces > 0) {
         const ModelShade& S = p.shade[h.model];
         mt = S.mat_type;
         mc = mk3(S.color[0], S.color[1], S.color[2]);
+        if (MAYTEX && p.tex) {
+            if (tri == kTriCached) {
+                const float4 a = p.cache_albedo[slot];
+                mc = mk3(a.x, a.y, a.z);
+            } else {
+                mc = hit_albedo(p, r.o, r.d, h.dist, h.model, tri);
+            }
+        }
     }
     shade_mat(r, h, iter, slot, mt, mc, p.env);
 }
@@ -1299,9 +1382,26 @@ __global__ __launch_bounds__(kBlock) void k_primary(KParams p) {
     if (i >= p.npix) return;
     f3 o, d;
     camera_ray(p, i, o, d);
-    const Hit h = intersect_scene<ACCEL, kBlock>(p, o, d, s_stack + threadIdx.x, s_hs + threadIdx.x);
+    int tri;
+    const Hit h = intersect_scene<ACCEL, kBlock>(p, o, d, s_stack + threadIdx.x, s_hs + threadIdx.x, tri);
     p.cache_hit[i] = make_float4(h.dist, h.n.x, h.n.y, h.n.z);
     p.cache_model[i] = h.model;
+    if (p.tex) {                                   // a kernel argument: wave-uniform
+        const f3 mc = h.model >= 0 ? hit_albedo(p, o, d, h.dist, h.model, tri) : mk3(0, 0, 0);
+        p.cache_albedo[i] = make_float4(mc.x, mc.y, mc.z, 0.0f);
+    }
+}
+
+// Test hook: the albedo definition for caller-given hits (ranges checked by the host).
+__global__ __launch_bounds__(kBlock) void k_hit_albedo(KParams p, int n, const float* orig, const float* dir,
+                                                       const float* dist, const int* model, const int* tri, float* rgb) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    f3 mc = mk3(0, 0, 0);
+    if (model[i] >= 0)
+        mc = hit_albedo(p, mk3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]), mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]),
+                        dist[i], model[i], tri[i]);
+    rgb[3 * i] = mc.x; rgb[3 * i + 1] = mc.y; rgb[3 * i + 2] = mc.z;
 }
 
 // Test hook: intersect an arbitrary batch of world-space rays.
@@ -2645,7 +2745,8 @@ __global__ __launch_bounds__(BS) void k_trace_deferred(KParams p, int bounce) {
 // SMOOTH: the hit-buffer pass of a scene with a smooth model (KParams::smooth set), its own
 // instantiation picked at launch, so the pass of every other scene keeps the registers it
 // had (42 VGPRs against 64); the other forms test the pointer where they compute a normal.
-template <bool FIRST, int ACCEL, int BS, bool SMOOTH = false>
+// TEX (with SMOOTH): the pass of a scene with a textured model (KParams::tex set), likewise.
+template <bool FIRST, int ACCEL, int BS, bool SMOOTH = false, bool TEX = false>
 __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_MINWAVES) void k_bounce(KParams p, int iter, int bounce) {
     __shared__ int s_stack[(!FIRST && ACCEL != ACCEL_GRID && ACCEL != kAccelHitBuffer) ? kStack * BS : 1];
     __shared__ int4 s_hs[(!FIRST && ACCEL == ACCEL_GRID_FAST) ? kHitCap * BS : 1];
@@ -2685,7 +2786,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             for (int q = 0; q < 9; q++) nm[q] = p.models[mi].nm[q];
             const ModelShade& S = p.shade[mi];
             const int mt = S.mat_type;
-            const f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
+            f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
             const float4 tn = tri >= 0 ? tnl : make_float4(0, 0, 0, 0);
             f3 hn = normalize(xform_normal9(nm, mk3(tn.x, tn.y, tn.z)));
             if (SMOOTH) {
@@ -2696,8 +2797,21 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
 #pragma unroll
                 for (int q = 0; q < 12; q++) w2m[q] = p.models[mi].w2m[q];
                 const int sm = S.smooth;
-                const f3 sn = smooth_normal(w2m, nm, T, r.o, r.d, hh.x, hn);
+                const Bary B = hit_bary(w2m, T, r.o, r.d, hh.x);
+                const f3 sn = smooth_normal(nm, T, B, hn);
                 hn = ((hm >= 0) & (tri >= 0) & (sm != 0)) ? sn : hn;
+                if (TEX) {
+                    // hit_albedo's values (keep the two in step); the model's texture index and its
+                    // texture record come in the round trip above (both indexed by the model), the
+                    // four taps (the buffer's first texel for an untextured hit) are one further round trip
+                    const int ti = S.texture;
+                    const int4 R = reinterpret_cast<const int4*>(p.tex)[mi];
+                    float u, v;
+                    hit_uv(T, B, u, v);
+                    const TexTaps t = tex_taps(R, u, v);
+                    const f3 tc = tex_blend(p.tex[t.a00], p.tex[t.a01], p.tex[t.a10], p.tex[t.a11], t.tx, t.ty, mc);
+                    mc = ((hm >= 0) & (tri >= 0) & (ti >= 0)) ? tc : mc;
+                }
             }
             h.dist = hh.x;
             h.model = hm;
@@ -2705,6 +2819,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             shade_mat(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc, p.env);
         }
     } else if (active) {
+        int tri = kTriCached;
         if (FIRST) {
             first_hit_state(p, j, r, h);
         } else {
@@ -2717,11 +2832,12 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             r = load_ray(p, in_buf, lo * BS + (j - p.blk_off[lo]));
             if (ACCEL == kAccelHitBuffer) {       // traced by k_trace_bvh / k_trace_gf
                 h = SMOOTH ? get_hit(p, j, r.o, r.d) : get_hit(p, j);
+                if (TEX) tri = __float_as_int(p.hit4[j].y);
             } else {
-                h = intersect_scene<ACCEL, BS>(p, r.o, r.d, s_stack + threadIdx.x, s_hs + threadIdx.x);
+                h = intersect_scene<ACCEL, BS>(p, r.o, r.d, s_stack + threadIdx.x, s_hs + threadIdx.x, tri);
             }
         }
-        shade(p, r, h, iter >= 0 ? iter : *p.iter_dev, j);   // -1: hipGraph replay reads the id
+        shade<TEX || FIRST || ACCEL != kAccelHitBuffer>(p, r, h, iter >= 0 ? iter : *p.iter_dev, j, tri);   // -1: hipGraph replay reads the id
     }
     const bool alive = active && r.bounces > 0;
     if (active && !alive) {
@@ -2771,7 +2887,7 @@ __global__ __launch_bounds__(BS, PT_MINWAVES) void k_bounce_masked(KParams p, in
     if (active) {
         Hit h;
         first_hit_state(p, j, r, h);
-        shade(p, r, h, iter, j);
+        shade(p, r, h, iter, j, kTriCached);
     }
     const bool alive = active && r.bounces > 0;
     if (inside && !alive) {
@@ -3309,9 +3425,21 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     // smooth shading: the flags as they are now (uploaded with model_shade above) and, only when
     // some model is smooth, the per-triangle table the hit normal interpolates from
     kp.smooth = nullptr;
-    bool any_smooth = false;
-    for (const ModelShade& sh : scene.model_shade) any_smooth |= sh.smooth != 0;
-    if (any_smooth) {
+    // albedo textures: the bindings as they are now (likewise) and, only when some model is
+    // textured, the texels and the vertex uvs, which ride in the same table
+    kp.tex = nullptr;
+    kp.cache_albedo = nullptr;
+    tex_bytes = 0;
+    alloc_ntris = (int)scene.triangles.size();
+    alloc_color.resize(scene.model_shade.size() * 3);
+    bool any_smooth = false, any_tex = false;
+    for (size_t i = 0; i < scene.model_shade.size(); i++) {
+        const ModelShade& sh = scene.model_shade[i];
+        any_smooth |= sh.smooth != 0;
+        any_tex |= sh.texture >= 0;
+        for (int k = 0; k < 3; k++) alloc_color[3 * i + k] = sh.color[k];
+    }
+    if (any_smooth || any_tex) {
         std::vector<TriShade> tab(std::max<size_t>(scene.triangles.size(), 1), TriShade{});   // record 0 always exists
         for (size_t t = 0; t < scene.triangles.size(); t++) {
             TriShade& q = tab[t];
@@ -3321,9 +3449,47 @@ int Renderer::allocateOnGPU(const Scene& scene) {
                 const f3 vn = scene.vertices[scene.triangles[t].vertex_indices[j]].normal;
                 nn[j][0] = vn.x; nn[j][1] = vn.y; nn[j][2] = vn.z; nn[j][3] = 0.0f;
             }
+            if (any_tex) {
+                float* lane[6] = {&q.v0[3], &q.e1[3], &q.e2[3], &q.n0[3], &q.n1[3], &q.n2[3]};
+                for (int j = 0; j < 3; j++) {
+                    const size_t vi = (size_t)scene.triangles[t].vertex_indices[j];
+                    *lane[2 * j] = scene.vertex_uv[2 * vi];
+                    *lane[2 * j + 1] = scene.vertex_uv[2 * vi + 1];
+                }
+            }
         }
         // the copy is enqueued from pageable memory: it is staged before the call returns
         PT_HIP(upload(allocs, &kp.smooth, tab.data(), tab.size() * sizeof(TriShade), stream));
+        if (any_tex) tex_bytes += tab.size() * sizeof(TriShade);
+    }
+    if (any_tex) {
+        // one buffer: a TexRec per model (its texture's place and size, so that the shading pass
+        // fetches it with the model's other records, not after its texture index), then every
+        // texture's texels as float4 (a tap is one 16-byte load)
+        const size_t ntex = scene.textures.size(), nrec = scene.model_shade.size();
+        size_t total = nrec;
+        std::vector<size_t> first(ntex);
+        for (size_t i = 0; i < ntex; i++) { first[i] = total; total += (size_t)scene.textures[i].w * scene.textures[i].h; }
+        if (total > 0x7fffffffull) { last_error = "allocateOnGPU: textures exceed 2^31 texels"; return -1; }
+        std::vector<float4> buf(total, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (size_t i = 0; i < ntex; i++) {
+            const Texture& t = scene.textures[i];
+            for (size_t q = 0; q < (size_t)t.w * t.h; q++)
+                buf[first[i] + q] = make_float4(t.rgb[3 * q], t.rgb[3 * q + 1], t.rgb[3 * q + 2], 0.0f);
+        }
+        for (size_t m = 0; m < nrec; m++) {
+            const int ti = scene.model_shade[m].texture;
+            // an untextured model: one texel at the buffer's first, which exists and is never used
+            const TexRec rec = ti >= 0 ? TexRec{(int)first[ti], scene.textures[ti].w, scene.textures[ti].h, 0}
+                                       : TexRec{(int)nrec, 1, 1, 0};
+            std::memcpy(&buf[m], &rec, sizeof rec);
+        }
+        float4* dev = nullptr;
+        PT_HIP(upload(allocs, &dev, buf.data(), buf.size() * sizeof(float4), stream));
+        PT_HIP(hipStreamSynchronize(stream));          // buf is pageable and dies here
+        kp.tex = dev;
+        PT_HIP(upload(allocs, &kp.cache_albedo, nullptr, cap * sizeof(float4), stream));
+        tex_bytes += buf.size() * sizeof(float4);
     }
     if (external_image) kp.image = ext_image;
     else PT_HIP(upload(allocs, &kp.image, nullptr, (size_t)npix_all * 3 * sizeof(float), stream));
@@ -3602,7 +3768,9 @@ void Renderer::launchTrace(const KParams& k, hipStream_t st, int b) {
 
 template <bool FIRST, int BS>
 static void launch_bounce_bs(int accel, dim3 grid, hipStream_t st, const KParams& kp, int iter, int b) {
-    if (accel == kAccelHitBuffer && kp.smooth && !FIRST)
+    if (accel == kAccelHitBuffer && kp.tex && !FIRST)
+        hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true, true>), grid, dim3(BS), 0, st, kp, iter, b);
+    else if (accel == kAccelHitBuffer && kp.smooth && !FIRST)
         hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true>), grid, dim3(BS), 0, st, kp, iter, b);
     else if (accel == kAccelHitBuffer)
         hipLaunchKernelGGL((k_bounce<FIRST, kAccelHitBuffer, BS>), grid, dim3(BS), 0, st, kp, iter, b);
@@ -4090,6 +4258,60 @@ int Renderer::primaryHits(float* dist, float* normal, int* model) {
         dist[i] = hit[i].x;
         normal[3 * i] = hit[i].y; normal[3 * i + 1] = hit[i].z; normal[3 * i + 2] = hit[i].w;
     }
+    return 0;
+}
+
+int Renderer::primaryAlbedo(float* rgb_out) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!cache_valid && launchPrimary() != 0) return -1;
+    const size_t npix_all = (size_t)cfg.width * cfg.height;
+    std::fill(rgb_out, rgb_out + npix_all * 3, 0.0f);                 // a miss, and a pixel tail_drop leaves out
+    if (kp.cache_albedo) {
+        std::vector<float4> a(kp.npix);
+        PT_HIP(hipMemcpyAsync(a.data(), kp.cache_albedo, kp.npix * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        PT_HIP(hipStreamSynchronize(stream));
+        for (int i = 0; i < kp.npix; i++) { rgb_out[3 * i] = a[i].x; rgb_out[3 * i + 1] = a[i].y; rgb_out[3 * i + 2] = a[i].z; }
+        return 0;
+    }
+    std::vector<int> model(kp.npix);                                  // no texture: the hit model's colour
+    PT_HIP(hipMemcpyAsync(model.data(), kp.cache_model, kp.npix * sizeof(int), hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < kp.npix; i++)
+        if (model[i] >= 0)
+            for (int k = 0; k < 3; k++) rgb_out[3 * i + k] = alloc_color[3 * (size_t)model[i] + k];
+    return 0;
+}
+
+int Renderer::hitAlbedo(int n, const float* orig, const float* dir, const float* dist, const int* model, const int* tri,
+                        float* rgb_out) {
+    if (!allocated) { last_error = "hit_albedo: not allocated"; return -1; }
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; i++) {                   // refused before any launch: the kernel indexes with these
+        if (model[i] >= kp.nmodels) { last_error = "hit_albedo: model index out of range"; return -1; }
+        if (model[i] >= 0 && (tri[i] < 0 || tri[i] >= alloc_ntris)) { last_error = "hit_albedo: triangle index out of range"; return -1; }
+    }
+    float* d_buf = nullptr;                         // orig 3n, dir 3n, dist n, model n, tri n, rgb 3n
+    PT_HIP(hipMalloc(&d_buf, (size_t)n * 48));
+    float* d_o = d_buf;
+    float* d_d = d_buf + 3 * (size_t)n;
+    float* d_t = d_buf + 6 * (size_t)n;
+    int* d_m = reinterpret_cast<int*>(d_buf + 7 * (size_t)n);
+    int* d_tri = d_m + n;
+    float* d_rgb = d_buf + 9 * (size_t)n;
+    hipError_t e = hipMemcpyAsync(d_o, orig, (size_t)n * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_t, dist, (size_t)n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_m, model, (size_t)n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tri, tri, (size_t)n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_hit_albedo, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, kp, n, d_o, d_d,
+                           d_t, d_m, d_tri, d_rgb);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    hipFree(d_buf);
+    if (e != hipSuccess) return fail(e, "hit_albedo");
     return 0;
 }
 

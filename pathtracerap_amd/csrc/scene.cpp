@@ -167,8 +167,13 @@ static void m3_inverse_of_m4(const float* m, float* out) {
 // Appends one aiMesh worth of data exactly like Scene::processMesh
 // (Scene.cpp:264-291): positions/normals scaled by BASE_MODEL_SCALE, bbox
 // updated per vertex, triangle indices offset by the mesh's first vertex.
-int Scene::addVertexRun(const std::vector<f3>& pos, const std::vector<f3>& nrm, const std::vector<int>& tri_local) {
+int Scene::addVertexRun(const std::vector<f3>& pos, const std::vector<f3>& nrm, const std::vector<int>& tri_local,
+                        const std::vector<float>* uv) {
     Mesh mesh;
+    vertex_uv.resize(vertices.size() * 2, 0.0f);
+    if (uv) vertex_uv.insert(vertex_uv.end(), uv->begin(), uv->end());
+    else vertex_uv.resize((vertices.size() + pos.size()) * 2, 0.0f);
+    mesh_has_uv.push_back(uv ? 1 : 0);
     mesh.vertex_indices.start_index = (int)vertices.size();
     for (size_t i = 0; i < pos.size(); i++) {
         Vertex v;
@@ -201,10 +206,13 @@ int Scene::loadObj(const std::string& path) {
     std::ifstream in(path);
     if (!in) { last_error = "Error loading mesh: cannot open " + path; return -1; }
     std::vector<f3> V, N, pos, nrm;
+    std::vector<float> VT, uv;                   // vt as stored: (u, 1 - v), aiProcess_FlipUVs
     std::vector<int> tri;
     std::string line;
     int base = 0;
+    bool any_vt = false;
     std::vector<std::pair<int, int>> corners;
+    std::vector<int> corner_vt;
     while (std::getline(in, line)) {
         if (line.size() < 2) continue;
         const char* s = line.c_str();
@@ -216,17 +224,27 @@ int Scene::loadObj(const std::string& path) {
             char* e;
             double x = std::strtod(s + 3, &e), y = std::strtod(e, &e), z = std::strtod(e, &e);
             N.push_back(mk3((float)x, (float)y, (float)z));
+        } else if (s[0] == 'v' && s[1] == 't' && (s[2] == ' ' || s[2] == '\t')) {
+            char* e;
+            double u = std::strtod(s + 3, &e), v = std::strtod(e, &e);
+            VT.push_back((float)u);
+            VT.push_back(1.0f - (float)v);
         } else if (s[0] == 'f' && (s[1] == ' ' || s[1] == '\t')) {
             corners.clear();
+            corner_vt.clear();
             std::istringstream ss(line.substr(2));
             std::string tok;
             while (ss >> tok) {
-                int vi = 0, ni = 0;
-                bool has_n = false;
+                int vi = 0, ni = 0, ti = 0;
+                bool has_n = false, has_t = false;
                 size_t p1 = tok.find('/');
                 vi = std::atoi(tok.substr(0, p1).c_str());
                 if (p1 != std::string::npos) {
                     size_t p2 = tok.find('/', p1 + 1);
+                    const std::string mid = tok.substr(p1 + 1, p2 == std::string::npos ? std::string::npos : p2 - p1 - 1);
+                    // a file with no vt line so far has nothing the index could name: it is ignored,
+                    // as it always was
+                    if (!mid.empty() && !VT.empty()) { ti = std::atoi(mid.c_str()); has_t = true; }
                     if (p2 != std::string::npos && p2 + 1 < tok.size()) {
                         ni = std::atoi(tok.substr(p2 + 1).c_str());
                         has_n = true;
@@ -234,11 +252,15 @@ int Scene::loadObj(const std::string& path) {
                 }
                 vi = vi > 0 ? vi - 1 : (int)V.size() + vi;
                 if (has_n) ni = ni > 0 ? ni - 1 : (int)N.size() + ni;
-                if (vi < 0 || vi >= (int)V.size() || (has_n && (ni < 0 || ni >= (int)N.size()))) {
+                if (has_t) ti = ti > 0 ? ti - 1 : (int)(VT.size() / 2) + ti;
+                if (vi < 0 || vi >= (int)V.size() || (has_n && (ni < 0 || ni >= (int)N.size())) ||
+                    (has_t && (ti < 0 || ti >= (int)(VT.size() / 2)))) {
                     last_error = "Error loading mesh: bad face index in " + path;
                     return -1;
                 }
                 corners.push_back({vi, has_n ? ni : -1});
+                corner_vt.push_back(has_t ? ti : -1);
+                any_vt |= has_t;
             }
             int k = (int)corners.size();
             if (k < 3) continue;
@@ -248,6 +270,8 @@ int Scene::loadObj(const std::string& path) {
             for (int j = 0; j < k; j++) {
                 pos.push_back(V[corners[j].first]);
                 nrm.push_back(corners[j].second >= 0 ? N[corners[j].second] : g);
+                uv.push_back(corner_vt[j] >= 0 ? VT[2 * corner_vt[j]] : 0.0f);
+                uv.push_back(corner_vt[j] >= 0 ? VT[2 * corner_vt[j] + 1] : 0.0f);
             }
             for (int j = 1; j + 1 < k; j++) {
                 tri.push_back(base);
@@ -257,7 +281,7 @@ int Scene::loadObj(const std::string& path) {
             base += k;
         }
     }
-    return addVertexRun(pos, nrm, tri);
+    return addVertexRun(pos, nrm, tri, any_vt ? &uv : nullptr);
 }
 
 int Scene::addMesh(const float* p, const float* n, int nv, const int* tris, int nt) {
@@ -298,6 +322,97 @@ int Scene::setModelSmooth(int model, bool on) {
 int Scene::modelSmooth(int model) const {
     if (model < 0 || model >= (int)models.size()) return -1;
     return models[model].smooth ? 1 : 0;
+}
+
+int Scene::setMeshUv(int mesh, const float* uv, int nv) {
+    if (mesh < 0 || mesh >= (int)meshes.size()) { last_error = "setMeshUv: bad mesh index"; return -1; }
+    const IndexRange& vr = meshes[mesh].vertex_indices;
+    if (nv != vr.end_index - vr.start_index) { last_error = "setMeshUv: nv is not the mesh's vertex count"; return -1; }
+    for (int i = 0; i < 2 * nv; i++)
+        if (!std::isfinite(uv[i])) { last_error = "setMeshUv: non-finite uv"; return -1; }
+    std::copy(uv, uv + 2 * (size_t)nv, vertex_uv.begin() + 2 * (size_t)vr.start_index);
+    mesh_has_uv[mesh] = 1;
+    return 0;
+}
+
+int Scene::meshHasUv(int mesh) const {
+    if (mesh < 0 || mesh >= (int)meshes.size()) return -1;
+    return mesh_has_uv[mesh] ? 1 : 0;
+}
+
+int Scene::addTexture(int w, int h, const float* rgb) {
+    if (w < 1 || h < 1 || w > 4096 || h > 4096) { last_error = "addTexture: width and height must be in [1,4096]"; return -1; }
+    const size_t n = (size_t)w * h * 3;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(rgb[i])) { last_error = "addTexture: non-finite texel"; return -1; }
+    Texture t;
+    t.w = w; t.h = h;
+    t.rgb.assign(rgb, rgb + n);
+    textures.push_back(std::move(t));
+    return (int)textures.size() - 1;
+}
+
+int Scene::setModelTexture(int model, int texture) {
+    if (model < -1 || model >= (int)models.size()) { last_error = "setModelTexture: bad model index"; return -1; }
+    if (texture < -1 || texture >= (int)textures.size()) { last_error = "setModelTexture: bad texture index"; return -1; }
+    const int lo = model < 0 ? 0 : model, hi = model < 0 ? (int)models.size() : model + 1;
+    if (texture >= 0)
+        for (int i = lo; i < hi; i++)
+            if (!mesh_has_uv[models[i].mesh_index]) { last_error = "setModelTexture: mesh has no uv"; return -1; }
+    for (int i = lo; i < hi; i++) {
+        models[i].texture = texture;
+        if (model_shade.size() == models.size()) model_shade[i].texture = texture;   // built: the binding alone changes
+    }
+    return 0;
+}
+
+int Scene::modelTexture(int model, int* out) const {
+    if (model < 0 || model >= (int)models.size()) return -1;
+    *out = models[model].texture;
+    return 0;
+}
+
+// Binary P6, maxval <= 255; a texel is (float)byte / (float)maxval, linear (no gamma decode).
+int Scene::loadPpm(const std::string& path) {
+    auto bad = [&](const char* why) { last_error = "Error loading texture: " + std::string(why) + " in " + path; return -1; };
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { last_error = "Error loading texture: cannot open " + path; return -1; }
+    std::string data((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    size_t pos = 0;
+    auto token = [&](std::string& out) {            // whitespace- and #-comment-separated header token
+        for (;;) {
+            while (pos < data.size() && std::isspace((unsigned char)data[pos])) pos++;
+            if (pos < data.size() && data[pos] == '#') { while (pos < data.size() && data[pos] != '\n') pos++; continue; }
+            break;
+        }
+        out.clear();
+        while (pos < data.size() && !std::isspace((unsigned char)data[pos])) out.push_back(data[pos++]);
+        return !out.empty();
+    };
+    std::string magic, tw, th, tm;
+    if (!token(magic) || magic != "P6") return bad("not a binary P6 file");
+    if (!token(tw) || !token(th) || !token(tm)) return bad("truncated header");
+    auto number = [](const std::string& t, long& v) {
+        if (t.empty() || t.size() > 9) return false;
+        for (char c : t) if (!std::isdigit((unsigned char)c)) return false;
+        v = std::atol(t.c_str());
+        return true;
+    };
+    long w, h, mv;
+    if (!number(tw, w) || !number(th, h) || !number(tm, mv)) return bad("bad header number");
+    if (w < 1 || h < 1 || w > 4096 || h > 4096) return bad("width and height must be in [1,4096]");
+    if (mv < 1 || mv > 255) return bad("maxval must be in [1,255]");
+    if (pos >= data.size() || !std::isspace((unsigned char)data[pos])) return bad("truncated header");
+    pos++;                                          // the single whitespace byte after maxval
+    const size_t n = (size_t)w * h * 3;
+    if (data.size() - pos < n) return bad("truncated pixel data");
+    std::vector<float> rgb(n);
+    for (size_t i = 0; i < n; i++) {
+        const unsigned char b = (unsigned char)data[pos + i];
+        if (b > mv) return bad("byte above maxval");
+        rgb[i] = (float)b / (float)mv;
+    }
+    return addTexture((int)w, (int)h, rgb.data());
 }
 
 // ---------------------------------------------------------------------------
@@ -342,7 +457,8 @@ static int material_from_name(const std::string& k) {
 
 // Generated primitives for the Config.txt SPHERE / BOX blocks (in OBJ units,
 // i.e. before BASE_MODEL_SCALE, like a loaded file).
-static void gen_box(const double* mx, const double* mn, std::vector<f3>& pos, std::vector<f3>& nrm, std::vector<int>& tri) {
+static void gen_box(const double* mx, const double* mn, std::vector<f3>& pos, std::vector<f3>& nrm, std::vector<int>& tri,
+                    std::vector<float>& tex) {
     const float lo[3] = {(float)mn[0], (float)mn[1], (float)mn[2]};
     const float hi[3] = {(float)mx[0], (float)mx[1], (float)mx[2]};
     for (int axis = 0; axis < 3; axis++)
@@ -361,13 +477,16 @@ static void gen_box(const double* mx, const double* mn, std::vector<f3>& pos, st
             for (int q = 0; q < 4; q++) {
                 pos.push_back(mk3(c[q][0], c[q][1], c[q][2]));
                 nrm.push_back(mk3(n[0], n[1], n[2]));
+                tex.push_back((float)uv[q][0]);
+                tex.push_back((float)uv[q][1]);
             }
             if (side) { tri.insert(tri.end(), {b, b + 1, b + 2, b, b + 2, b + 3}); }
             else { tri.insert(tri.end(), {b, b + 2, b + 1, b, b + 3, b + 2}); }
         }
 }
 
-static void gen_sphere(double radius, const double* ctr, std::vector<f3>& pos, std::vector<f3>& nrm, std::vector<int>& tri) {
+static void gen_sphere(double radius, const double* ctr, std::vector<f3>& pos, std::vector<f3>& nrm, std::vector<int>& tri,
+                       std::vector<float>& tex) {
     const int NU = 48, NV = 24;
     for (int j = 0; j <= NV; j++)
         for (int i = 0; i <= NU; i++) {
@@ -375,6 +494,8 @@ static void gen_sphere(double radius, const double* ctr, std::vector<f3>& pos, s
             double nx = std::sin(th) * std::cos(ph), ny = std::cos(th), nz = std::sin(th) * std::sin(ph);
             pos.push_back(mk3((float)(ctr[0] + radius * nx), (float)(ctr[1] + radius * ny), (float)(ctr[2] + radius * nz)));
             nrm.push_back(mk3((float)nx, (float)ny, (float)nz));
+            tex.push_back((float)((double)i / NU));
+            tex.push_back((float)((double)j / NV));
         }
     for (int j = 0; j < NV; j++)
         for (int i = 0; i < NU; i++) {
@@ -409,6 +530,7 @@ int Scene::loadConfig(const std::string& path) {
     struct Mat { int type; float color[3]; };
     std::map<std::string, Mat> mats;
     std::map<std::string, int> named_mesh;   // OBJ name or path -> mesh index
+    std::map<std::string, int> named_tex;    // TEXTURE name -> texture index
     auto resolve = [&](const std::string& p) { return (!p.empty() && p[0] == '/') ? p : dir + "/" + p; };
     auto fail = [&](const std::string& msg) { last_error = path + ": " + msg; return -2; };
 
@@ -422,11 +544,32 @@ int Scene::loadConfig(const std::string& path) {
             Mat m; m.type = mt;
             for (int i = 0; i < 3; i++) m.color[i] = (float)c[i];
             mats[b[1]] = m;
+        } else if (kw == "TEXTURE") {
+            if (b.size() < 4) return fail("TEXTURE block needs name, kind and data");
+            int t = -1;
+            if (b[2] == "CHECKER") {
+                std::vector<double> c0, c1;
+                if (b.size() < 6 || !parse_vec(b[3], c0) || !parse_vec(b[4], c1) || c0.size() != 3 || c1.size() != 3)
+                    return fail("TEXTURE CHECKER needs [r,g,b], [r,g,b] and N");
+                char* end = nullptr;
+                const long n = std::strtol(b[5].c_str(), &end, 10);
+                if (!end || *end != 0 || n < 1 || n > 4096) return fail("TEXTURE CHECKER size must be in [1,4096]: " + b[5]);
+                std::vector<float> rgb((size_t)n * n * 3);
+                for (long y = 0; y < n; y++)
+                    for (long x = 0; x < n; x++)
+                        for (int k = 0; k < 3; k++) rgb[3 * ((size_t)y * n + x) + k] = (float)(((x + y) & 1) ? c1[k] : c0[k]);
+                t = addTexture((int)n, (int)n, rgb.data());
+                if (t < 0) return fail(last_error);
+            } else if (b[2] == "PPM") {
+                t = loadPpm(resolve(b[3]));
+                if (t < 0) return -3;
+            } else return fail("unknown TEXTURE kind " + b[2]);
+            named_tex[b[1]] = t;
         }
     }
     for (auto& b : blocks) {
         const std::string& kw = b[0];
-        if (material_from_name(kw) >= 0) continue;
+        if (material_from_name(kw) >= 0 || kw == "TEXTURE") continue;
         if (kw == "RENDER") {
             bool has_eye = false, has_target = false, any_cam = false;
             for (size_t i = 1; i < b.size(); i++) {
@@ -486,21 +629,22 @@ int Scene::loadConfig(const std::string& path) {
             std::vector<double> mx, mn;
             if (b.size() < 4 || !parse_vec(b[2], mx) || !parse_vec(b[3], mn) || mx.size() != 3 || mn.size() != 3)
                 return fail("BOX needs [max] and [min]");
-            std::vector<f3> pos, nrm; std::vector<int> tri;
-            gen_box(mx.data(), mn.data(), pos, nrm, tri);
-            mesh = addVertexRun(pos, nrm, tri);
+            std::vector<f3> pos, nrm; std::vector<int> tri; std::vector<float> tex;
+            gen_box(mx.data(), mn.data(), pos, nrm, tri, tex);
+            mesh = addVertexRun(pos, nrm, tri, &tex);
             first_attr = 4;
         } else {                           // Config.txt:1-7: SPHERE name radius [center]
             std::vector<double> c;
             if (b.size() < 4 || !parse_vec(b[3], c) || c.size() != 3) return fail("SPHERE needs radius and [center]");
-            std::vector<f3> pos, nrm; std::vector<int> tri;
-            gen_sphere(std::atof(b[2].c_str()), c.data(), pos, nrm, tri);
-            mesh = addVertexRun(pos, nrm, tri);
+            std::vector<f3> pos, nrm; std::vector<int> tri; std::vector<float> tex;
+            gen_sphere(std::atof(b[2].c_str()), c.data(), pos, nrm, tri, tex);
+            mesh = addVertexRun(pos, nrm, tri, &tex);
             first_attr = 4;
         }
         float scale[3] = {1, 1, 1}, rot[3] = {0, 0, 0}, tr[3] = {0, 0, 0};
         Mat mat; mat.type = MAT_DIFFUSE; mat.color[0] = mat.color[1] = mat.color[2] = 0.98f;
         bool smooth = false;
+        int texture = -1;
         for (size_t i = first_attr; i < b.size(); i++) {
             std::string key = b[i].substr(0, b[i].find(':'));
             std::string val = b[i].find(':') == std::string::npos ? "" : trim(b[i].substr(b[i].find(':') + 1));
@@ -509,6 +653,12 @@ int Scene::loadConfig(const std::string& path) {
                 auto it = mats.find(val);
                 if (it == mats.end()) return fail("unknown material " + val);
                 mat = it->second;
+                continue;
+            }
+            if (key == "texture") {
+                auto it = named_tex.find(val);
+                if (it == named_tex.end()) return fail("unknown texture " + val);
+                texture = it->second;
                 continue;
             }
             if (key == "shading") {
@@ -526,6 +676,7 @@ int Scene::loadConfig(const std::string& path) {
         const int model = addModel(mesh, scale, rot, tr, mat.type, mat.color);
         if (model < 0) return -4;
         models[model].smooth = smooth;
+        if (texture >= 0 && setModelTexture(model, texture) < 0) return fail(last_error);
     }
     if (models.empty()) return fail("scene has no MESH/BOX/SPHERE instances");
     return 0;
@@ -647,6 +798,7 @@ void Scene::buildDeviceTables() {
         for (int k = 0; k < 3; k++) sh.color[k] = m.mat.color[k];
         sh.mat_type = m.mat.material_type;
         sh.smooth = m.smooth ? 1 : 0;
+        sh.texture = m.texture;
         world_box(m, mesh, r.bvh_root, r.wbox);
         // Bounded hit-set collection (ACCEL_GRID_FAST).  A member h whose voxel box the
         // DDA enters at ray parameter tau has its hit within tau + R_h, R_h = the diameter

@@ -14,7 +14,7 @@
 
 namespace pt {
 
-struct Vertex { f3 position; f3 normal; };            // Primitive.h:23-28 (uv unused)
+struct Vertex { f3 position; f3 normal; };            // Primitive.h:23-28 (its uv: Scene::vertex_uv)
 struct Triangle { int vertex_indices[3]; };            // Primitive.h:30-33
 struct BoundingBox {                                   // Primitive.h:35-60
     f3 min = {kFMax, kFMax, kFMax};
@@ -38,7 +38,9 @@ struct Model {                                          // Primitive.h:94-101
     float world_to_model[16];
     Material mat;
     bool smooth = false;                                // setModelSmooth: shade with interpolated vertex normals
+    int texture = -1;                                   // setModelTexture: index into Scene::textures, -1: none
 };
+struct Texture { int w = 0, h = 0; std::vector<float> rgb; };   // w*h texels, texel (y, x) at 3*(y*w + x); linear values
 struct Voxel { IndexRange entity_index_range; int entity_type = ENTITY_TRIANGLE; };  // Primitive.h:123-127
 struct Grid {                                           // Primitive.h:129-139
     IndexRange voxelIndices;
@@ -76,6 +78,15 @@ public:
     // so far.  Any time after the model exists; the grid and the BLAS are not touched.
     int setModelSmooth(int model, bool on);
     int modelSmooth(int model) const;                   // 0 / 1, negative: bad index
+    // Albedo textures (no counterpart in the reference, whose Primitive.h declares a uv and never
+    // reads it).  Per-vertex uv of one mesh, in addMesh's vertex order; the grid and the BLAS are
+    // not touched.  A texture is w x h RGB texels; a model binds one (-1: none; model -1: every
+    // model added so far), before or after build.
+    int setMeshUv(int mesh, const float* uv, int nv);
+    int meshHasUv(int mesh) const;                      // 0 / 1, negative: bad index
+    int addTexture(int w, int h, const float* rgb);     // -> texture index
+    int setModelTexture(int model, int texture);
+    int modelTexture(int model, int* out) const;        // 0, negative: bad index
     // addMeshesToGrid (Scene.cpp:318-396) + device tables.  `grid_dim` = GRID_X/Y/Z.
     int build(const int grid_dim[3], bool with_bvh);
     // The BLAS on demand: Renderer::allocateOnGPU calls this for the accels that
@@ -87,6 +98,9 @@ public:
     std::vector<Mesh> meshes;
     std::vector<Vertex> vertices;
     std::vector<Triangle> triangles;
+    std::vector<float> vertex_uv;                       // 2 floats / vertex, (0, 0) where the mesh has no uv
+    std::vector<char> mesh_has_uv;                      // per mesh
+    std::vector<Texture> textures;
     std::vector<Grid> grids;
     std::vector<Voxel> voxels;
     std::vector<int> per_voxel_data_pool;
@@ -97,7 +111,7 @@ public:
     std::vector<float> tri_geom;      // 12 floats / triangle: v0.xyz,_, e1.xyz,_, e2.xyz,_
     std::vector<float> tri_normal;    // 4 floats / triangle: normalize((n0+n1+n2)*(1/3))
     std::vector<ModelRec> model_recs;
-    std::vector<ModelShade> model_shade;  // per model: material and smooth flag (shading pass)
+    std::vector<ModelShade> model_shade;  // per model: material, smooth flag and texture (shading pass)
     std::vector<BvhNode> bvh_nodes;   // all meshes' BLAS, concatenated
     std::vector<int> bvh_tri_order;   // leaf triangle references (global triangle index)
     std::vector<float> bvh_tri_geom;  // 12 floats / leaf reference: tri_geom in leaf order; w lanes carry
@@ -113,7 +127,8 @@ public:
 
 private:
     int addVertexRun(const std::vector<f3>& pos, const std::vector<f3>& nrm,
-                     const std::vector<int>& tri_local);
+                     const std::vector<int>& tri_local, const std::vector<float>* uv = nullptr);
+    int loadPpm(const std::string& path);               // binary P6 -> texture index
     void addMeshesToGrid();
     void buildDeviceTables();
     void buildBvh(int mesh);
