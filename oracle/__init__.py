@@ -15,10 +15,16 @@ What lives here:
 * ``reference_scene``: the hard-coded scene of Scene::Scene (Scene.cpp:3-224).
 * ``build_scene``: model matrices (glm restatement) + addMeshesToGrid.
 
-Pinning: the reference is unbuildable here (CUDA toolkit, thrust, Assimp), so
-the oracle is pinned against the reference's own output image
-``PathTracerAP/Render.bmp`` (1000x800, ITER=500, Scene.cpp scene), committed
-as ``tests/golden/reference_render_1000x800_500.npz`` -- see
+* ``reference_code`` (binding of ``_ref/libptref.so``): the reference's own
+  device functions, kernel bodies and grid builder compiled for the host by
+  ``make -C oracle`` when the reference tree is present (``ref/bridge.cpp``).
+  ``tests/test_reference_code.py`` holds the restatement to it bit for bit,
+  from the library or from recordings of its answers.
+
+Pinning: the reference as a whole program (CUDA launches, Assimp) does not
+build here, so end to end the oracle is pinned against the reference's own
+output image ``PathTracerAP/Render.bmp`` (1000x800, ITER=500, Scene.cpp
+scene), committed as ``tests/golden/reference_render_1000x800_500.npz`` -- see
 ``tests/test_oracle_golden.py`` and ``tests/golden/make_golden.py``.
 """
 from __future__ import annotations
@@ -365,6 +371,45 @@ def render(scene: FlatScene, cfg: RenderConfig, image: np.ndarray | None = None)
     if rc != 0:
         raise RuntimeError("ptor_render failed")
     return image, seg.value
+
+
+def render_bounces(scene: FlatScene, cfg: RenderConfig, live_cap: int = 8):
+    """render, also returning the rays entering each bounce summed over the
+    iterations: (image, segments, live (live_cap,) i64)."""
+    image = np.zeros((cfg.width * cfg.height, 3), np.float32)
+    live = np.zeros(live_cap, np.int64)
+    cs = scene.c()
+    cc = cfg.c()
+    seg = ctypes.c_longlong(0)
+    rc = lib().ptor_render_bounces(ctypes.byref(cs), ctypes.byref(cc), _fp(image), ctypes.byref(seg),
+                                   live.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), live_cap)
+    if rc != 0:
+        raise RuntimeError("ptor_render_bounces failed")
+    return image, seg.value, live
+
+
+def transform(kind: int, m16, v):
+    """transformPosition (0) / transformDirection (1) / transformNormal (2) of a batch."""
+    m16 = np.ascontiguousarray(m16, np.float32).reshape(16)
+    v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+    out = np.zeros_like(v)
+    if lib().ptor_transform(kind, len(v), _fp(m16), _fp(v), _fp(out)) != 0:
+        raise RuntimeError("ptor_transform failed")
+    return out
+
+
+def shade(iter_, slot, orig, dirs, color, bounces, hit_dist, hit_normal, hit_type, hit_color):
+    """ptor_shade over a batch: new (orig, dir, color, bounces)."""
+    orig = np.array(orig, np.float32).reshape(-1, 3); dirs = np.array(dirs, np.float32).reshape(-1, 3)
+    color = np.array(color, np.float32).reshape(-1, 3); bounces = np.array(bounces, np.int32)
+    slot = np.ascontiguousarray(slot, np.int32); hit_dist = np.ascontiguousarray(hit_dist, np.float32)
+    hit_normal = np.ascontiguousarray(hit_normal, np.float32); hit_type = np.ascontiguousarray(hit_type, np.int32)
+    hit_color = np.ascontiguousarray(hit_color, np.float32)
+    rc = lib().ptor_shade(len(orig), int(iter_), _ip(slot), _fp(orig), _fp(dirs), _fp(color), _ip(bounces),
+                          _fp(hit_dist), _fp(hit_normal), _ip(hit_type), _fp(hit_color))
+    if rc != 0:
+        raise RuntimeError("ptor_shade failed")
+    return orig, dirs, color, bounces
 
 
 def intersect_primary(scene: FlatScene, cfg: RenderConfig):

@@ -621,8 +621,27 @@ int ptor_shade(int n, int iter, const int *slot, float *orig, float *dir, float 
     return 0;
 }
 
-/* renderLoop (Renderer.cpp:567-648) */
 int ptor_render(const ptor_scene *s, const ptor_config *c, float *image, long long *segments) {
+    return ptor_render_bounces(s, c, image, segments, NULL, 0);
+}
+
+/* transformPosition / transformDirection / transformNormal (utility.h:71-88) */
+int ptor_transform(int kind, int n, const float *m16, const float *v, float *out) {
+    for (int i = 0; i < n; i++) {
+        v3 p = mk(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+        v3 r;
+        if (kind == 0) r = xform(m16, p, 1.0f);
+        else if (kind == 1) r = xform(m16, p, 0.0f);
+        else if (kind == 2) r = xform_normal(m16, p);
+        else return -1;
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+    return 0;
+}
+
+/* renderLoop (Renderer.cpp:567-648) */
+int ptor_render_bounces(const ptor_scene *s, const ptor_config *c, float *image, long long *segments,
+                        long long *live, int live_cap) {
     int n_total = c->width * c->height;
     /* dim3 blocks = ceil(nrays / 32) with integer division (Renderer.cpp:573):
      * the trailing nrays % 32 rays are never launched.  Optional. */
@@ -635,6 +654,7 @@ int ptor_render(const ptor_scene *s, const ptor_config *c, float *image, long lo
     if (!rays || !tmp || !isect || !cache || !alive) { free(rays); free(tmp); free(isect); free(cache); free(alive); return -1; }
     set_threads(c->threads);
     long long seg = 0;
+    for (int i = 0; i < live_cap; i++) live[i] = 0;
     /* dev_ray_data starts zero-filled (vector<Ray>): never-launched rays gather 0. */
     for (int it = 0; it < c->iterations; it++) {
         int iter = c->first_iter + it;
@@ -646,6 +666,7 @@ int ptor_render(const ptor_scene *s, const ptor_config *c, float *image, long lo
         int ib = 0;
         for (;;) {
             seg += nrays;
+            if (ib < live_cap) live[ib] += nrays;
             if (ib == 0) {
                 if (it == 0) {
                     /* computeRaySceneIntersectionKernel then cache (Renderer.cpp:603-612) */

@@ -8,10 +8,13 @@
  * This is a plain-C restatement of the reference's algorithm
  * (purvakulkarni15/PathTracerAP, CUDA + glm 0.9.6 + thrust), written from
  * a reading of its sources.  Every function cites the reference file:line
- * it follows.  The reference itself is unbuildable in this image (needs the
- * CUDA toolkit, thrust and Assimp), so the oracle is pinned against the
- * reference's own golden output (PathTracerAP/Render.bmp, 1000x800, 500
- * iterations, the Scene.cpp scene) -- see tests/test_oracle_golden.py.
+ * it follows.  The reference as a whole program does not build here (CUDA
+ * kernel launches, Assimp), but the parts restated below do: ref/bridge.cpp
+ * compiles the reference's own device functions, kernel bodies and grid
+ * builder for the host, and tests/test_reference_code.py holds this file to
+ * them bit for bit.  The oracle is also pinned against the reference's golden
+ * output (PathTracerAP/Render.bmp, 1000x800, 500 iterations, the Scene.cpp
+ * scene) -- see tests/test_oracle_golden.py.
  *
  * Data layout deliberately mirrors the reference (Primitive.h structs,
  * array-of-structs ray pool, stable partition of the ray pool after every
@@ -61,6 +64,11 @@ typedef struct {
 int ptor_render(const ptor_scene *s, const ptor_config *c, float *image,
                 long long *segments);
 
+/* ptor_render, also reporting the rays that enter each bounce, summed over
+ * the iterations, in live[0..live_cap) (their sum is *segments). */
+int ptor_render_bounces(const ptor_scene *s, const ptor_config *c, float *image,
+                        long long *segments, long long *live, int live_cap);
+
 /* Primary-ray intersection only (computeRaySceneIntersectionKernel on the
  * camera rays, Renderer.cpp:364-409): per pixel dist, normal[3], model id
  * (-1 = miss).  Used by the unit parity tests. */
@@ -94,6 +102,10 @@ int ptor_build_grids(int nmesh, const int *mesh_ranges, const float *mesh_bbox,
                      int nmodel, int *model_ints, const int gdim[3],
                      int *ngrid, int *grid_ints, float *grid_vw,
                      int *nvox, int *vox, int pv_cap, int *npv, int *per_voxel);
+
+/* transformPosition (kind 0), transformDirection (1) and transformNormal (2)
+ * of utility.h:71-88 over a batch, one column-major matrix. */
+int ptor_transform(int kind, int n, const float *m16, const float *v, float *out);
 
 /* Self-contained math used by the oracle (exposed for the conformance test). */
 float ptor_sinf(float x);

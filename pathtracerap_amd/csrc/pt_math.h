@@ -86,8 +86,13 @@ PT_HD f3 xform_normal9(const float* nm, f3 n) {
 
 // ---------------------------------------------------------------------------
 // Transcendentals.  CUDA's sinf/cosf/powf are replaced by double-precision
-// polynomial evaluations rounded once to float (correctly rounded in all
-// sampled cases, so within 1 ulp of the reference's device functions).
+// polynomial evaluations rounded once to float.  What was checked: on 100,000
+// arguments each (sin and cos over [0, 2 pi), pow(x, 1/31) over [0, 1)) the
+// result equals the host libm's float64 value rounded to float
+// (tests/test_reference_code.py), and the reference's own scatter code built
+// over these functions equals the oracle bit for bit.  CUDA's device functions
+// were not run; their documented error bounds (a few ulp) are the distance
+// this leaves to the reference's CUDA build.
 // ---------------------------------------------------------------------------
 PT_HD double dfloor(double q) {
     double t = (double)(long long)q;

@@ -309,6 +309,19 @@ def model_count_spec(k, seed=7):
     return meshes, models
 
 
+SEVEN_MATERIALS = ["DIFFUSE", "SPECULAR", "REFLECTIVE", "REFRACTIVE", "EMISSIVE", "COAT", "METAL"]
+
+
+def seven_material_spec(k=15, seed=11):
+    """model_count_spec's room and k - 1 boxes, the boxes' materials cycling through
+    all seven types: SPECULAR and REFRACTIVE too, for which the reference's shading
+    has no branch (the ray keeps its origin and direction and loses a bounce)."""
+    meshes, models = model_count_spec(k, seed)
+    for i, m in enumerate(models[1:]):
+        m["material"] = SEVEN_MATERIALS[i % 7]
+    return meshes, models
+
+
 def scene_from_spec(P, meshes, models, grid=(25, 25, 25)):
     s = P.Scene()
     ids = [s.addMesh(*m) for m in meshes]
