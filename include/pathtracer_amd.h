@@ -199,10 +199,10 @@ int pt_scene_model_smooth(const pt_scene *s, int model);
  * the same bits.  No load leaves the texture: fl lies in [-1, n-1], so i0 and i1 lie in [0, n-1]
  * for every float input, a NaN and fr*n rounding up to n included.
  * Limits.  No mip levels and no ray differentials: minification aliases, and pixel jitter is the
- * remedy.  Texels are linear values; a PPM's bytes are not gamma-decoded.  The denoiser does not
- * demodulate albedo: inside one model only its luminance term stops at texture detail, so a
- * strong filter blurs the pattern; pt_renderer_primary_albedo is the input a later
- * demodulation would need.
+ * remedy.  Texels are linear values; a PPM's bytes are not gamma-decoded.  pt_renderer_denoise
+ * filters the image as it stands, so inside one model only its luminance term stops at texture
+ * detail; pt_renderer_denoise_ex with PT_DENOISE_DEMODULATE divides the primary hit's albedo out
+ * first (see there).
  * Config grammar: a block TEXTURE / <name> / CHECKER / [r,g,b] / [r,g,b] / N makes an N x N
  * texture, 1 <= N <= 4096, whose texel (y, x) is the first colour when x + y is even and the
  * second otherwise; TEXTURE / <name> / PPM / <path> loads a binary P6 file with maxval <= 255
@@ -418,10 +418,62 @@ int pt_renderer_denoise(pt_renderer *r, int samples, const pt_denoise_params *p,
  * conversion: bytes (int)(D * 255.0f) & 0xFF, rows bottom-up.  No counterpart in the reference. */
 int pt_renderer_render_image_denoised(pt_renderer *r, const char *bmp_path, int samples,
                                       const pt_denoise_params *p);
-/* HIP-event times in ms of the last pt_renderer_denoise made with pt_renderer_set_profiling
- * on: ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy into device_rgb_out,
- * ms[8] first kernel to last; n values (0 beyond 9).  No counterpart in the reference. */
+/* HIP-event times in ms of the last pt_renderer_denoise or pt_renderer_denoise_ex made with
+ * pt_renderer_set_profiling on: ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy into
+ * device_rgb_out, ms[8] first kernel to last, ms[9] the remodulation of PT_DENOISE_DEMODULATE (0:
+ * not run); n values (0 beyond 10).  No counterpart in the reference. */
 int pt_renderer_denoise_times(pt_renderer *r, double *ms, int n);
+
+/* ---- The denoiser with options: albedo demodulation, and per-tile sample counts (added within
+ * ABI 9: new functions only; pt_renderer_denoise, pt_denoise_params and PT_ABI_VERSION are
+ * unchanged, and a caller who never uses these allocates, launches and computes what it did.  No
+ * counterpart in the reference). ----
+ * pt_renderer_denoise_ex with flags == 0 is pt_renderer_denoise: the same launches and the same
+ * bits.  Otherwise it is pt_renderer_denoise's definition above with the changes below, float32
+ * IEEE in exactly this order, no fused multiply-add.
+ * PT_DENOISE_DEMODULATE.  The image holds sqrt(color) per channel, and the first shade of a
+ * DIFFUSE, METAL, COAT, EMISSIVE or REFLECTIVE hit multiplies the colour by the albedo mc, so a
+ * pixel's contribution is sqrt(mc) * sqrt(rest), channel by channel: the albedo divides out
+ * exactly.  For pixel p with guide model k_p >= 0 let A be the three floats
+ * pt_renderer_primary_albedo reports for p (the albedo plane's value when the allocation has
+ * textures, otherwise the colour of model k_p).  Per channel:
+ *   t = A > 0 ? A : 0    (a NaN gives 0);   sa = sqrtf(t);   e = sa > 1e-3f ? sa : 1e-3f
+ * For k_p < 0 (a miss, or a pixel tail_drop left out) sa = e = 1.0f: such a pixel shows the
+ * environment and is not demodulated.  Prep computes m_k and v_k as above, then
+ *   c_k = m_k / e_k;   v'_k = v_k / (e_k * e_k)   (the product rounded first);
+ *   V = (v'_r + v'_g) + v'_b
+ * The passes are unchanged: every guide, weight and the luminance L is taken from the demodulated
+ * c.  After the last pass  D_k = c_k * sa_k.  Multiplying by sa, not e, keeps a black texel black
+ * when its neighbours bleed irradiance into it.  The result everywhere (the renderer's own
+ * buffer, device_rgb_out, host_rgb, the BMP) is D; host_var is the last pass's V, in demodulated
+ * units.  The floor 1e-3 is part of the definition, like den_l's 1e-4: a sqrt-space albedo of
+ * 1e-3 is below a quarter of one output byte step (D * 255).
+ * PT_DENOISE_TILE_COUNTS.  nf of pixel (x, y) is (float)counts[(y/16)*tiles_x + x/16], the counts
+ * pt_renderer_sample_counts reports, wherever prep uses nf (nf - 1.0f included); the passes are
+ * unchanged.  This is how an image of masked or adaptive iterations is denoised.
+ * Refused before any launch: pt_renderer_denoise's refusals with the same text (without
+ * PT_DENOISE_TILE_COUNTS, mixed sample counts included); "denoise_ex: unknown flag bits";
+ * "denoise_ex: PT_DENOISE_TILE_COUNTS takes every tile's own sample count; samples must be <= 0";
+ * "denoise_ex: PT_DENOISE_TILE_COUNTS needs at least 2 samples in every tile";
+ * "denoise_ex: PT_DENOISE_DEMODULATE needs max_bounces >= 1 (without a bounce no hit multiplies
+ * by its albedo)".
+ * Cost: no buffer beyond pt_renderer_denoise's; demodulation reads 16 bytes more per pixel in
+ * prep (the albedo plane; without textures the model's colour) and adds one launch that
+ * multiplies the result in place; the counts are one int per tile, uploaded per call.  No
+ * atomics: a call repeats bit for bit.  PT_DENOISE_LDS keeps its meaning.
+ * Limits.  Under pixel jitter or a lens the albedo is the pinhole centre ray's, like the other
+ * guides: a defocused or jittered textured region is demodulated with an albedo that its samples
+ * did not all see.  Only the first hit's albedo is removed: a texture seen in a mirror is filtered
+ * as before.  A first hit on a SPECULAR or REFRACTIVE model, whose shade multiplies by nothing, is
+ * divided by an albedo its samples do not contain and multiplied by it again: harmless for a
+ * plain colour, a reason to leave the flag off for a textured model of such a material. */
+#define PT_DENOISE_DEMODULATE  1   /* filter the image divided by the primary hit's sqrt(albedo) */
+#define PT_DENOISE_TILE_COUNTS 2   /* nf per pixel = its 16x16 tile's own sample count */
+int pt_renderer_denoise_ex(pt_renderer *r, int samples, const pt_denoise_params *p, int flags,
+                           float *device_rgb_out, float *host_rgb, float *host_var);
+/* pt_renderer_denoise_ex, then the BMP of D as pt_renderer_render_image_denoised writes it. */
+int pt_renderer_render_image_denoised_ex(pt_renderer *r, const char *bmp_path, int samples,
+                                         const pt_denoise_params *p, int flags);
 
 /* ---- Tile-masked sampling and the adaptive render (added within ABI 9: new functions only;
  * pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in the reference, which

@@ -34,6 +34,16 @@ ACCEL_BVH = 1
 ACCEL_GRID_FAST = 2
 NOISE_TILE = 16     # PT_NOISE_TILE: Renderer.noise()'s tile edge in pixels
 DENOISE_MAX_PASSES = 6     # PT_DENOISE_MAX_PASSES
+DENOISE_DEMODULATE = 1     # PT_DENOISE_DEMODULATE (pt_renderer_denoise_ex's flags)
+DENOISE_TILE_COUNTS = 2    # PT_DENOISE_TILE_COUNTS
+
+
+def _denoise_flags(demodulate, tile_counts, flags):
+    if flags is not None:
+        return int(flags)
+    return (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TILE_COUNTS if tile_counts else 0)
+
+
 # renderer.h: segments[] slots after the per-bounce counters, as segments_per_bounce indices
 _MAX_BOUNCE_COUNTERS = 64
 _DEFERRED_SLOT = 50 + _MAX_BOUNCE_COUNTERS - 1     # kDeferredRayCounter
@@ -151,6 +161,10 @@ EXPORTS = [
     ("pt_renderer_render_image_denoised", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int,
                                                          ctypes.POINTER(_DenoiseParams)]),
     ("pt_renderer_denoise_times", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+    ("pt_renderer_denoise_ex", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_DenoiseParams), ctypes.c_int,
+                                              ctypes.c_void_p, _P_F, _P_F]),
+    ("pt_renderer_render_image_denoised_ex", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int,
+                                                            ctypes.POINTER(_DenoiseParams), ctypes.c_int]),
     ("pt_renderer_render_loop_masked", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_ubyte)]),
     ("pt_renderer_sample_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
@@ -767,7 +781,8 @@ class Renderer:
         return bool(rc), done.value, mean.value
 
     def denoise(self, samples: int | None = None, passes: int = 5, sigma_l: float = 4.0, sigma_z: float = 1.0,
-                out_ptr: int | None = None, keepalive=None, variance: bool = False):
+                out_ptr: int | None = None, keepalive=None, variance: bool = False, demodulate: bool = False,
+                tile_counts: bool = False, flags: int | None = None):
         """Variance-guided edge-avoiding filter of the accumulated mean image
         (include/pathtracer_amd.h, pt_renderer_denoise; needs enable_moments) -> the
         denoised (W*H, 3) float32 image, with ``variance=True`` (image, var (W*H,)).
@@ -775,29 +790,45 @@ class Renderer:
         caller who reduced shards into bound tensors passes the total).  ``out_ptr``: a
         caller-owned W*H*3 float device buffer (a torch tensor, kept alive by
         ``keepalive``) that receives the image too.  The image and the moments are not
-        modified."""
+        modified.  ``demodulate``: filter the image divided by the primary hit's albedo and
+        multiply it back (DENOISE_DEMODULATE); ``tile_counts``: divide by each tile's own
+        sample count, after masked or adaptive iterations (DENOISE_TILE_COUNTS); either
+        goes through pt_renderer_denoise_ex, as does an explicit ``flags`` word."""
         self._denoise_ref = keepalive
         p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
         img = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
         var = np.zeros(self.cfg.width * self.cfg.height, np.float32) if variance else None
-        _err(lib().pt_renderer_denoise(self._h, int(samples or 0), ctypes.byref(p),
-                                       ctypes.c_void_p(int(out_ptr)) if out_ptr else None, _fp(img),
-                                       _fp(var) if variance else None), "denoise")
+        out = ctypes.c_void_p(int(out_ptr)) if out_ptr else None
+        if flags is None and not demodulate and not tile_counts:
+            _err(lib().pt_renderer_denoise(self._h, int(samples or 0), ctypes.byref(p), out, _fp(img),
+                                           _fp(var) if variance else None), "denoise")
+        else:
+            _err(lib().pt_renderer_denoise_ex(self._h, int(samples or 0), ctypes.byref(p),
+                                              _denoise_flags(demodulate, tile_counts, flags), out, _fp(img),
+                                              _fp(var) if variance else None), "denoise")
         return (img, var) if variance else img
 
     def renderImageDenoised(self, path: str = "Render.bmp", samples: int | None = None, passes: int = 5,
-                            sigma_l: float = 4.0, sigma_z: float = 1.0) -> None:
-        """The BMP of the denoised mean (renderImage's conversion of D * 255)."""
+                            sigma_l: float = 4.0, sigma_z: float = 1.0, demodulate: bool = False,
+                            tile_counts: bool = False, flags: int | None = None) -> None:
+        """The BMP of the denoised mean (renderImage's conversion of D * 255); ``demodulate``,
+        ``tile_counts`` and ``flags`` as for denoise()."""
         p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
-        _err(lib().pt_renderer_render_image_denoised(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p)),
-             "renderImageDenoised")
+        if flags is None and not demodulate and not tile_counts:
+            _err(lib().pt_renderer_render_image_denoised(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p)),
+                 "renderImageDenoised")
+        else:
+            _err(lib().pt_renderer_render_image_denoised_ex(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p),
+                                                            _denoise_flags(demodulate, tile_counts, flags)),
+                 "renderImageDenoised")
 
     def denoise_times(self) -> dict:
         """HIP-event times (ms) of the last denoise() made with set_profiling on: ``prep``,
-        ``passes`` (one per pass run), ``out`` (the copy into ``out_ptr``) and ``total``."""
-        ms = (ctypes.c_double * 9)()
-        _err(lib().pt_renderer_denoise_times(self._h, ms, 9), "denoise_times")
-        return dict(prep=ms[0], passes=[ms[1 + i] for i in range(DENOISE_MAX_PASSES)], out=ms[7], total=ms[8])
+        ``passes`` (one per pass run), ``out`` (the copy into ``out_ptr``), ``total`` and
+        ``remod`` (the remodulation of ``demodulate``; 0 when not run)."""
+        ms = (ctypes.c_double * 10)()
+        _err(lib().pt_renderer_denoise_times(self._h, ms, 10), "denoise_times")
+        return dict(prep=ms[0], passes=[ms[1 + i] for i in range(DENOISE_MAX_PASSES)], out=ms[7], total=ms[8], remod=ms[9])
 
     def _tiles(self):
         return (self.cfg.height + NOISE_TILE - 1) // NOISE_TILE, (self.cfg.width + NOISE_TILE - 1) // NOISE_TILE

@@ -405,6 +405,21 @@ int pt_renderer_render_image_denoised(pt_renderer* r, const char* path, int samp
     if (p) d = *p;
     R_CALL(r->r->renderImageDenoised(path, samples, d.passes, d.sigma_l, d.sigma_z));
 }
+int pt_renderer_denoise_ex(pt_renderer* r, int samples, const pt_denoise_params* p, int flags, float* device_rgb_out,
+                           float* host_rgb, float* host_var) {
+    pt_denoise_params d;
+    pt_default_denoise_params(&d);
+    if (p) d = *p;
+    R_CALL(r->r->denoiseEx(samples, d.passes, d.sigma_l, d.sigma_z, flags, device_rgb_out, host_rgb, host_var));
+}
+int pt_renderer_render_image_denoised_ex(pt_renderer* r, const char* path, int samples, const pt_denoise_params* p,
+                                         int flags) {
+    if (!path) return set_err("bad arguments");
+    pt_denoise_params d;
+    pt_default_denoise_params(&d);
+    if (p) d = *p;
+    R_CALL(r->r->renderImageDenoised(path, samples, d.passes, d.sigma_l, d.sigma_z, flags));
+}
 int pt_renderer_denoise_times(pt_renderer* r, double* ms, int n) {
     if (!ms || n < 0) return set_err("bad arguments");
     R_CALL(r->r->denoiseTimes(ms, n));

@@ -206,7 +206,8 @@ __global__ __launch_bounds__(256) void k_mean_counts(const float* __restrict__ S
 // (depth, world normal, model).  include/pathtracer_amd.h (pt_renderer_denoise)
 // states the arithmetic; the kernels keep its float32 operations and their order
 // (IEEE add, multiply, divide, square root; -ffp-contract=off), so the result
-// equals the numpy restatement in tests/denoise_ref.py bit for bit.
+// equals the numpy restatement in tests/denoise_ref.py bit for bit.  pt_renderer_denoise_ex adds
+// two options to prep, and a remodulation after the last pass (tests/denoise_albedo_ref.py).
 //
 // Per-pixel records, built once per call by k_denoise_prep: (c.rgb, V) ping-pong,
 // (n.xyz, d), the model and the depth slope.  No atomics: a call repeats bit for bit.
@@ -220,11 +221,50 @@ __device__ inline float dn_depth(const float4* __restrict__ cache_hit, int npix,
     return idx < (size_t)npix ? cache_hit[idx].x : FLT_MAX;
 }
 
-// One pixel's records from its sums s, q (3 floats each).
-__device__ inline void dn_prep_pixel(size_t p, const float* s, const float* q, float nf,
+// pt_renderer_denoise_ex, PT_DENOISE_DEMODULATE: per channel the sqrt-space albedo sa of pixel
+// p's primary hit on model k, and the divisor e = max(sa, 1e-3f).  A is what
+// pt_renderer_primary_albedo reports: the albedo plane's texel when the allocation has textures
+// (`plane`), else the model's colour.  Both are kernel arguments, so the choice is wave-uniform.
+// k < 0 (a miss, or a pixel tail_drop left out; the plane ends at the traced count): sa = e = 1.
+__device__ inline void dn_sqrt_albedo(int k, size_t p, const float4* __restrict__ plane,
+                                      const ModelShade* __restrict__ shade, float* sa, float* e) {
+    if (k < 0) {
+        for (int c = 0; c < 3; c++) sa[c] = e[c] = 1.0f;
+        return;
+    }
+    float a[3];
+    if (plane) {
+        const float4 t = plane[p];
+        a[0] = t.x; a[1] = t.y; a[2] = t.z;
+    } else {
+        for (int c = 0; c < 3; c++) a[c] = shade[k].color[c];
+    }
+    for (int c = 0; c < 3; c++) {
+        const float t = a[c] > 0.0f ? a[c] : 0.0f;      // a NaN gives 0
+        sa[c] = sqrtf(t);
+        e[c] = sa[c] > 1e-3f ? sa[c] : 1e-3f;
+    }
+}
+
+// What the variants of k_denoise_prep read beyond the plain one's arguments.
+struct DnPrepOpt {
+    const float4* albedo;       // DEMOD: the albedo plane (KParams::cache_albedo), or null:
+    const ModelShade* shade;    // ... the models' colours
+    const int* counts;          // COUNTS: samples per 16 x 16 tile
+    int tiles_x;
+};
+
+// One pixel's records from its sums s, q (3 floats each).  DEMOD: c and the channel variances
+// divided by the primary hit's sqrt-space albedo.  COUNTS: nf is the pixel's tile's own count.
+template <bool DEMOD, bool COUNTS>
+__device__ inline void dn_prep_pixel(size_t p, const float* s, const float* q, float nf, const DnPrepOpt& opt,
                                      const float4* __restrict__ cache_hit, const int* __restrict__ cache_model, int npix,
                                      int W, int H, float4* __restrict__ cv, float4* __restrict__ nd,
                                      int* __restrict__ model, float* __restrict__ slope) {
+    if (COUNTS) {
+        const int ty = (int)(p / (size_t)W), tx = (int)(p - (size_t)ty * W);
+        nf = (float)opt.counts[(ty / kTile) * opt.tiles_x + (tx / kTile)];
+    }
     float m[3], v[3];
     for (int k = 0; k < 3; k++) {
         m[k] = s[k] / nf;
@@ -232,6 +272,14 @@ __device__ inline void dn_prep_pixel(size_t p, const float* s, const float* q, f
         float t = qq - m[k] * m[k];
         t = t > 0.0f ? t : 0.0f;
         v[k] = t / (nf - 1.0f);
+    }
+    if (DEMOD) {
+        float sa[3], e[3];
+        dn_sqrt_albedo(p < (size_t)npix ? cache_model[p] : -1, p, opt.albedo, opt.shade, sa, e);
+        for (int k = 0; k < 3; k++) {
+            m[k] = m[k] / e[k];
+            v[k] = v[k] / (e[k] * e[k]);
+        }
     }
     cv[p] = make_float4(m[0], m[1], m[2], (v[0] + v[1]) + v[2]);
     const bool live = p < (size_t)npix;
@@ -248,12 +296,16 @@ __device__ inline void dn_prep_pixel(size_t p, const float* s, const float* q, f
 
 // VEC: a lane takes 4 pixels = 3 float4 of S and of Q (16-byte aligned S and Q; the last
 // npixels % 4 pixels go one per lane); otherwise one pixel per lane, scalar reads.
-template <bool VEC>
+// DEMOD, COUNTS: pt_renderer_denoise_ex's options; <VEC, false, false> is pt_renderer_denoise's
+// prep and reads nothing of `opt`.  DEMOD adds one float4 of the albedo plane per pixel (a lane's
+// 4 pixels are 64 consecutive bytes) or, without textures, a gather of the model's colour; COUNTS
+// one int per pixel, the same for 16 consecutive pixels of a row.
+template <bool VEC, bool DEMOD, bool COUNTS>
 __global__ __launch_bounds__(256) void k_denoise_prep(const float* __restrict__ S, const float* __restrict__ Q, float nf,
                                                       const float4* __restrict__ cache_hit,
                                                       const int* __restrict__ cache_model, int npix, int W, int H,
                                                       float4* __restrict__ cv, float4* __restrict__ nd,
-                                                      int* __restrict__ model, float* __restrict__ slope) {
+                                                      int* __restrict__ model, float* __restrict__ slope, DnPrepOpt opt) {
     const size_t n = (size_t)W * H;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (VEC) {
@@ -267,18 +319,19 @@ __global__ __launch_bounds__(256) void k_denoise_prep(const float* __restrict__ 
                 q[4 * k] = b.x; q[4 * k + 1] = b.y; q[4 * k + 2] = b.z; q[4 * k + 3] = b.w;
             }
             for (int k = 0; k < 4; k++)
-                dn_prep_pixel(4 * i + k, s + 3 * k, q + 3 * k, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+                dn_prep_pixel<DEMOD, COUNTS>(4 * i + k, s + 3 * k, q + 3 * k, nf, opt, cache_hit, cache_model, npix, W, H,
+                                             cv, nd, model, slope);
         }
         if (i < (n & 3)) {
             const size_t p = (n4 << 2) + i;
             const float s[3] = {S[3 * p], S[3 * p + 1], S[3 * p + 2]};
             const float q[3] = {Q[3 * p], Q[3 * p + 1], Q[3 * p + 2]};
-            dn_prep_pixel(p, s, q, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+            dn_prep_pixel<DEMOD, COUNTS>(p, s, q, nf, opt, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
         }
     } else if (i < n) {
         const float s[3] = {S[3 * i], S[3 * i + 1], S[3 * i + 2]};
         const float q[3] = {Q[3 * i], Q[3 * i + 1], Q[3 * i + 2]};
-        dn_prep_pixel(i, s, q, nf, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
+        dn_prep_pixel<DEMOD, COUNTS>(i, s, q, nf, opt, cache_hit, cache_model, npix, W, H, cv, nd, model, slope);
     }
 }
 
@@ -397,6 +450,21 @@ __global__ __launch_bounds__(256) void k_denoise_out(const float4* __restrict__ 
         const float4 c = cv[i];
         rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
     }
+}
+
+// PT_DENOISE_DEMODULATE, after the last pass: D = c * sa in place, one lane per pixel; V stays
+// (demodulated units).  sa is recomputed from prep's source (sqrtf is correctly rounded, so it is
+// prep's value) and the model prep recorded; a pixel with k < 0 has sa = 1 and keeps its bits.
+__global__ __launch_bounds__(256) void k_denoise_remod(float4* __restrict__ cv, const int* __restrict__ model, size_t n,
+                                                       const float4* __restrict__ albedo,
+                                                       const ModelShade* __restrict__ shade) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float sa[3], e[3];
+    dn_sqrt_albedo(model[i], i, albedo, shade, sa, e);
+    float4 c = cv[i];
+    c.x = c.x * sa[0]; c.y = c.y * sa[1]; c.z = c.z * sa[2];
+    cv[i] = c;
 }
 
 // ---------------------------------------------------------------------------
@@ -546,13 +614,53 @@ static void launchDenoisePass(bool stage, dim3 grid, hipStream_t st, const float
     else hipLaunchKernelGGL((k_denoise_pass<STEP, false>), grid, dim3(kTileWG), 0, st, in, out, nd, model, slope, W, H, tiles_x, sl, sz);
 }
 
+template <bool VEC>
+static void launchDenoisePrep(int flags, dim3 grid, hipStream_t st, const float* S, const float* Q, float nf,
+                              const float4* cache_hit, const int* cache_model, int npix, int W, int H, float4* cv,
+                              float4* nd, int* model, float* slope, const DnPrepOpt& opt) {
+#define PT_PREP(D, C) \
+    hipLaunchKernelGGL((k_denoise_prep<VEC, D, C>), grid, dim3(256), 0, st, S, Q, nf, cache_hit, cache_model, npix, W, H, \
+                       cv, nd, model, slope, opt)
+    switch (flags & (PT_DENOISE_DEMODULATE | PT_DENOISE_TILE_COUNTS)) {
+        case 0: PT_PREP(false, false); break;
+        case PT_DENOISE_DEMODULATE: PT_PREP(true, false); break;
+        case PT_DENOISE_TILE_COUNTS: PT_PREP(false, true); break;
+        default: PT_PREP(true, true); break;
+    }
+#undef PT_PREP
+}
+
 int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, float* device_rgb_out, float* host_rgb,
                       float* host_var) {
+    return denoiseEx(samples, passes, sigma_l, sigma_z, 0, device_rgb_out, host_rgb, host_var);
+}
+
+// flags 0: pt_renderer_denoise, launch for launch.  PT_DENOISE_DEMODULATE: prep divides by the
+// primary hit's sqrt-space albedo and k_denoise_remod multiplies the last pass's colour by it, in
+// the result buffer, before anything reads that.  PT_DENOISE_TILE_COUNTS: prep's nf is each
+// tile's own sample count (the counts go up on the stream first, as for adaptiveNoise).
+int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, int flags, float* device_rgb_out,
+                        float* host_rgb, float* host_var) {
     if (!allocated) { last_error = "not allocated"; return -1; }
     if (!moments_on) { last_error = "moments not enabled"; return -1; }
-    if (samples <= 0 && !countsUniform()) return refuseMixedCounts("denoise");
-    if (samples <= 0) samples = samples_accumulated;
-    if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
+    const bool demod = (flags & PT_DENOISE_DEMODULATE) != 0, by_tile = (flags & PT_DENOISE_TILE_COUNTS) != 0;
+    if (flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_TILE_COUNTS)) { last_error = "denoise_ex: unknown flag bits"; return -1; }
+    if (by_tile && samples > 0) {
+        last_error = "denoise_ex: PT_DENOISE_TILE_COUNTS takes every tile's own sample count; samples must be <= 0";
+        return -1;
+    }
+    if (demod && cfg.max_bounces < 1) {
+        last_error = "denoise_ex: PT_DENOISE_DEMODULATE needs max_bounces >= 1 (without a bounce no hit multiplies by its albedo)";
+        return -1;
+    }
+    if (by_tile) {
+        for (int c : tile_counts)
+            if (c < 2) { last_error = "denoise_ex: PT_DENOISE_TILE_COUNTS needs at least 2 samples in every tile"; return -1; }
+    } else {
+        if (samples <= 0 && !countsUniform()) return refuseMixedCounts("denoise");
+        if (samples <= 0) samples = samples_accumulated;
+        if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
+    }
     if (passes < 1 || passes > PT_DENOISE_MAX_PASSES || !std::isfinite(sigma_l) || !(sigma_l > 0.0f) ||
         !std::isfinite(sigma_z) || !(sigma_z > 0.0f)) {
         last_error = "bad denoise parameters";
@@ -569,12 +677,14 @@ int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, flo
     }
     if (allocDenoise() != 0) return -1;
     if (!cache_valid && launchPrimary() != 0) return -1;
+    if (by_tile && uploadTileCounts() != 0) return -1;
     const int W = cfg.width, H = cfg.height;
     const size_t n = (size_t)W * H;
     // HIP events around every kernel when profiling is on (denoiseTimes)
     for (hipEvent_t ev : dn_events) hipEventDestroy(ev);
     dn_events.clear();
     dn_event_passes = 0;
+    dn_event_remod = false;
     const bool timed = profiling != 0;
     auto mark = [&]() -> int {
         if (!timed) return 0;
@@ -585,20 +695,21 @@ int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, flo
         return 0;
     };
     if (mark() != 0) return -1;
+    const int tx = noiseTilesX();
+    const DnPrepOpt opt = {demod ? kp.cache_albedo : nullptr, demod ? kp.shade : nullptr,
+                           by_tile ? tile_counts_dev : nullptr, tx};
     const bool vec = (((uintptr_t)kp.image | (uintptr_t)m2) & 15) == 0;
     if (vec) {
         const size_t n4 = n >> 2;
-        hipLaunchKernelGGL(k_denoise_prep<true>, dim3((unsigned)std::max<size_t>(1, (n4 + 255) / 256)), dim3(256), 0, stream,
-                           kp.image, m2, (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd,
-                           dn_model, dn_slope);
+        launchDenoisePrep<true>(flags, dim3((unsigned)std::max<size_t>(1, (n4 + 255) / 256)), stream, kp.image, m2,
+                                (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd, dn_model,
+                                dn_slope, opt);
     } else {
-        hipLaunchKernelGGL(k_denoise_prep<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           kp.image, m2, (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd,
-                           dn_model, dn_slope);
+        launchDenoisePrep<false>(flags, dim3((unsigned)((n + 255) / 256)), stream, kp.image, m2, (float)samples,
+                                 kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd, dn_model, dn_slope, opt);
     }
     PT_HIP(hipGetLastError());
     if (mark() != 0) return -1;
-    const int tx = noiseTilesX();
     const dim3 grid((unsigned)(tx * noiseTilesY()));
     for (int s = 0; s < passes; s++) {
         const float4* in = dn_cv[s & 1];
@@ -617,7 +728,14 @@ int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, flo
         if (mark() != 0) return -1;
     }
     dn_event_passes = timed ? passes : 0;
-    const float4* result = dn_cv[passes & 1];
+    float4* result = dn_cv[passes & 1];
+    if (demod) {
+        hipLaunchKernelGGL(k_denoise_remod, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, result, dn_model, n,
+                           kp.cache_albedo, kp.shade);
+        PT_HIP(hipGetLastError());
+        if (mark() != 0) return -1;
+        dn_event_remod = timed;
+    }
     if (device_rgb_out) {
         hipLaunchKernelGGL(k_denoise_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, result, n, device_rgb_out);
         PT_HIP(hipGetLastError());
@@ -638,13 +756,15 @@ int Renderer::denoise(int samples, int passes, float sigma_l, float sigma_z, flo
 }
 
 // ms[0] prep, ms[1..6] the passes (0: not run), ms[7] the copy to the caller's device
-// buffer, ms[8] first kernel to last: of the last denoise call made with profiling on.
+// buffer, ms[8] first kernel to last, ms[9] the remodulation (0: not run): of the last
+// denoise call made with profiling on.
 int Renderer::denoiseTimes(double* ms, int n) {
-    if (dn_event_passes == 0 || (int)dn_events.size() != dn_event_passes + 3) {
+    const int extra = dn_event_remod ? 1 : 0;
+    if (dn_event_passes == 0 || (int)dn_events.size() != dn_event_passes + 3 + extra) {
         last_error = "no timed denoise call (set_profiling, then denoise)";
         return -1;
     }
-    double v[9] = {};
+    double v[10] = {};
     auto span = [&](int a, int b) {
         float t = 0.0f;
         hipEventElapsedTime(&t, dn_events[a], dn_events[b]);
@@ -652,16 +772,18 @@ int Renderer::denoiseTimes(double* ms, int n) {
     };
     v[0] = span(0, 1);
     for (int s = 0; s < dn_event_passes; s++) v[1 + s] = span(1 + s, 2 + s);
-    v[7] = span(dn_event_passes + 1, dn_event_passes + 2);
-    v[8] = span(0, dn_event_passes + 2);
-    for (int i = 0; i < n; i++) ms[i] = i < 9 ? v[i] : 0.0;
+    if (extra) v[9] = span(dn_event_passes + 1, dn_event_passes + 2);
+    v[7] = span(dn_event_passes + 1 + extra, dn_event_passes + 2 + extra);
+    v[8] = span(0, dn_event_passes + 2 + extra);
+    for (int i = 0; i < n; i++) ms[i] = i < 10 ? v[i] : 0.0;
     return 0;
 }
 
 // The denoised mean D through renderImage's writer: bytes of D * 255.
-int Renderer::renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z) {
+int Renderer::renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z,
+                                  int flags) {
     std::vector<float> img((size_t)cfg.width * cfg.height * 3);
-    if (denoise(samples, passes, sigma_l, sigma_z, nullptr, img.data(), nullptr) != 0) return -1;
+    if (denoiseEx(samples, passes, sigma_l, sigma_z, flags, nullptr, img.data(), nullptr) != 0) return -1;
     return writeBmp(path, img.data(), 1.0f);         // x * 1.0f is x
 }
 

@@ -3,7 +3,7 @@
 //
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
-//                  [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
+//                  [--denoise-albedo] [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
 //                  [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] [--focus D] [--lens R]]
 //                  [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]
 //
@@ -37,7 +37,9 @@
 //
 // --denoise: keep the second moments and write the BMP of the denoised mean
 // (pt_renderer_render_image_denoised over the iterations actually rendered, N a-trous
-// passes, default 5) instead of the raw mean.
+// passes, default 5) instead of the raw mean.  --denoise-albedo implies --denoise and filters the
+// image with the primary hit's albedo divided out (pt_renderer_render_image_denoised_ex with
+// PT_DENOISE_DEMODULATE), so a texture is not blurred.
 //
 // Default: PT_ACCEL_GRID_FAST (the reference grid's image, bit for bit) with 16
 // iterations in flight, each on its own HIP stream and hardware queue.
@@ -56,7 +58,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
-                             "[--denoise [--denoise-passes N]] [--adaptive X [--check-every N] [--min-iter N]] "
+                             "[--denoise [--denoise-passes N]] [--denoise-albedo] [--adaptive X [--check-every N] [--min-iter N]] "
                              "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
                              "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]\n", argv[0]);
         return 2;
@@ -72,6 +74,7 @@ int main(int argc, char** argv) {
     double adaptive_target = -1.0;       // >= 0: tile-based adaptive sampling
     int min_iter = 2;
     bool denoise = false;
+    int denoise_flags = 0;
     bool jitter = false;
     float jitter_width = 1.0f;
     bool has_from = false, has_at = false, has_focus = false, cam_opt = false;
@@ -105,6 +108,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--ground") && i + 3 < argc) { vec3(ground, i); has_ground = true; }
         else if (!std::strcmp(argv[i], "--smooth")) smooth = true;
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[i], "--denoise-albedo")) { denoise = true; denoise_flags |= PT_DENOISE_DEMODULATE; }
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
     }
@@ -181,7 +185,8 @@ int main(int argc, char** argv) {
     long long seg = pt_renderer_segments(r);
     std::printf("Full run: %.0f microseconds, %lld ray segments, %.2f Mrays/s\n", us, seg, seg / us);
     if ((adaptive_target >= 0 ? pt_renderer_render_image_adaptive(r, out)
-         : denoise ? pt_renderer_render_image_denoised(r, out, iters, &dn) : pt_renderer_render_image(r, out, iters)) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+         : denoise ? (denoise_flags ? pt_renderer_render_image_denoised_ex(r, out, iters, &dn, denoise_flags)
+                                 : pt_renderer_render_image_denoised(r, out, iters, &dn)) : pt_renderer_render_image(r, out, iters)) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer_free(r);
     pt_scene_destroy(s);
     return 0;

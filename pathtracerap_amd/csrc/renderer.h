@@ -198,7 +198,13 @@ public:
     // in the reference); the image and the moments are read only
     int denoise(int samples, int passes, float sigma_l, float sigma_z, float* device_rgb_out, float* host_rgb,
                 float* host_var);
-    int renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z);
+    // denoise with options (pt_renderer_denoise_ex): PT_DENOISE_DEMODULATE filters the image divided by the
+    // primary hit's sqrt-space albedo and multiplies it back afterwards; PT_DENOISE_TILE_COUNTS divides by
+    // each tile's own sample count, so an image of masked or adaptive iterations can be filtered.  flags 0 is denoise
+    int denoiseEx(int samples, int passes, float sigma_l, float sigma_z, int flags, float* device_rgb_out,
+                  float* host_rgb, float* host_var);
+    int renderImageDenoised(const std::string& path, int samples, int passes, float sigma_l, float sigma_z,
+                            int flags = 0);
     int denoiseTimes(double* ms, int n);             // HIP-event times of the last denoise call under setProfiling
     // Tile-masked sampling and the adaptive render (no counterpart in the reference): iterations whose
     // first bounce emits only the rays of the active 16 x 16 tiles, per-tile sample counts, the estimate
@@ -294,6 +300,7 @@ private:
     float* dn_slope = nullptr;       // depth slope
     std::vector<hipEvent_t> dn_events;   // profiling: around prep, each pass and the output copy
     int dn_event_passes = 0;
+    bool dn_event_remod = false;         // ... and the remodulation (PT_DENOISE_DEMODULATE)
     std::vector<int> tile_counts;        // samples per noise tile since allocateOnGPU / clearImage (host)
     static constexpr int kMaskSlots = 4;     // masked calls whose mask copy may be in flight at once
     unsigned char* tile_mask_dev = nullptr;  // the mask the enqueued masked iterations read; set by the first masked call
