@@ -463,17 +463,77 @@ int pt_renderer_denoise_times(pt_renderer *r, double *ms, int n);
  * atomics: a call repeats bit for bit.  PT_DENOISE_LDS keeps its meaning.
  * Limits.  Under pixel jitter or a lens the albedo is the pinhole centre ray's, like the other
  * guides: a defocused or jittered textured region is demodulated with an albedo that its samples
- * did not all see.  Only the first hit's albedo is removed: a texture seen in a mirror is filtered
+ * did not all see (without PT_DENOISE_SAMPLED_GUIDES; with it the albedo is the mean over the
+ * samples' own first hits, see pt_renderer_enable_guides).  Only the first hit's albedo is removed: a texture seen in a mirror is filtered
  * as before.  A first hit on a SPECULAR or REFRACTIVE model, whose shade multiplies by nothing, is
  * divided by an albedo its samples do not contain and multiplied by it again: harmless for a
  * plain colour, a reason to leave the flag off for a textured model of such a material. */
 #define PT_DENOISE_DEMODULATE  1   /* filter the image divided by the primary hit's sqrt(albedo) */
 #define PT_DENOISE_TILE_COUNTS 2   /* nf per pixel = its 16x16 tile's own sample count */
+#define PT_DENOISE_SAMPLED_GUIDES 4 /* guides = means of the samples' first hits (pt_renderer_enable_guides) */
 int pt_renderer_denoise_ex(pt_renderer *r, int samples, const pt_denoise_params *p, int flags,
                            float *device_rgb_out, float *host_rgb, float *host_var);
 /* pt_renderer_denoise_ex, then the BMP of D as pt_renderer_render_image_denoised writes it. */
 int pt_renderer_render_image_denoised_ex(pt_renderer *r, const char *bmp_path, int samples,
                                          const pt_denoise_params *p, int flags);
+
+/* ---- Sampled first-hit guides (added within ABI 9: new functions and one new flag bit only;
+ * PT_ABI_VERSION is unchanged.  No counterpart in the reference).  Off unless enabled: a renderer
+ * that never calls pt_renderer_enable_guides allocates, launches and computes exactly what it did.
+ * Under pixel jitter or a lens the primary-hit cache, the unjittered pinhole ray's hit, is not what
+ * a pixel's samples saw.  With guides on, every generated iteration (one whose camera rays
+ * k_gen_jitter / k_gen_camera emit: the jitter on, or lens_radius > 0) adds one record g per
+ * emitted ray to G, a per-pixel record of 8 floats, 32 bytes, interleaved; for pixel p
+ *   G[8p .. 8p+7] = (Nx, Ny, Nz, Z, Ar, Ag, Ab, Hc)
+ * float32 IEEE, in this order, no fused multiply-add.  The ray's first hit is pass 1's hit record
+ * (distance t, model m, triangle tri):
+ *   hit (m >= 0):  n = the world normal pass 1's shade uses (the transformed triangle normal, or
+ *                  pt_scene_set_model_smooth's interpolated one); mc = the albedo of
+ *                  pt_scene_set_model_texture's definition (the model's colour without a texture);
+ *                  pos(a) = a > 0 ? a : 0;
+ *                  g = (n.x, n.y, n.z, t, sqrtf(pos(mc.r)), sqrtf(pos(mc.g)), sqrtf(pos(mc.b)), 1.0f)
+ *   miss:          g = eight zeros
+ * G[p] += g, one add per float, in iteration order: like S and Q the sums do not depend on the
+ * pipeline count, and a run repeats bit for bit (no atomics).  A pixel that emitted no ray (a tile
+ * a mask switched off, a pixel tail_drop left out) receives nothing.  The square root of the
+ * albedo is summed because a sample's contribution is sqrt(mc) * sqrt(rest).  Ordinary iterations
+ * (pinhole, jitter off) add nothing; the renderer counts per tile the samples that did
+ * (pt_renderer_guide_counts), beside pt_renderer_sample_counts.
+ * pt_renderer_enable_guides: before allocate_on_gpu.  device_ptr is a caller-owned device buffer of
+ * W*H*8 floats (4-byte alignment suffices; 16-byte alignment takes the faster merge), NULL: the
+ * renderer allocates it.  Refused for a null renderer and after allocation.  allocate_on_gpu then
+ * refuses guides without pt_renderer_enable_moments, and (a limit) guides without the split trace,
+ * whose hit records they read: PT_ACCEL_GRID, PT_GF_SPLIT=0 or PT_TRACE_SPLIT=0.
+ * pt_renderer_read_guides copies G to the host (it waits for the renderer's stream);
+ * pt_renderer_guide_counts writes tiles_y * tiles_x counts (NULL: none) and returns that number.
+ * pt_renderer_clear_image, and every call that does what it does (pt_renderer_set_camera, a new
+ * environment), zeroes G and the guide counts too.
+ * PT_DENOISE_SAMPLED_GUIDES (pt_renderer_denoise_ex, pt_renderer_render_image_denoised_ex; free to
+ * combine with the other two flags) changes prep alone; the passes and PT_DENOISE_LDS are
+ * untouched.  With nf the pixel's sample count (per tile under PT_DENOISE_TILE_COUNTS) and h = Hc:
+ *   validity, model:  k = h > 0 ? 0 : -1: the passes' model test becomes "both pixels saw a
+ *                     surface", and a pixel no sample hit copies through as a miss does
+ *   depth:            d = h > 0 ? Z / h : FLT_MAX; the slope g from these d by the same formula
+ *   normal:           n = (Nx / h, Ny / h, Nz / h), not renormalised: a pixel that mixes
+ *                     orientations has a short normal, its dot^64 weight to every neighbour falls,
+ *                     and it is filtered less, never across
+ *   demodulation (with PT_DENOISE_DEMODULATE), per channel:
+ *                     sa = (A + (nf - h)) / nf  (the sum rounded before the division: a sample
+ *                     that missed counts as albedo 1);  e = sa > 1e-3f ? sa : 1e-3f;
+ *                     c, v' and D = c * sa as defined above, with this sa also where h = 0
+ * Refused before any launch: "guides not enabled" (a renderer without pt_renderer_enable_guides
+ * knows the bit no more than it did: the message begins "denoise_ex: unknown flag bits" and names
+ * the reason); with samples <= 0, a tile whose guide count
+ * differs from its sample count (every sample since the last clear must be a generated iteration);
+ * with samples > 0 the caller vouches for that, as for sharded sums.
+ * Memory: 32 bytes per pixel for G and 32 per pixel per pipeline for the per-iteration records: at
+ * 1280 x 1024 42 MB + 16 x 42 MB = 713 MB when on, 0 when off.
+ * Limits.  The model test is hit / no hit: two models that meet at equal depth and normal are
+ * separated by the luminance term alone.  Only generated iterations accumulate.  No guides on the
+ * fused or list-walking trace paths.  Only the first hit's albedo is removed, as before. */
+int pt_renderer_enable_guides(pt_renderer *r, void *device_ptr);
+int pt_renderer_read_guides(pt_renderer *r, float *out);
+int pt_renderer_guide_counts(pt_renderer *r, int *tiles);
 
 /* ---- Tile-masked sampling and the adaptive render (added within ABI 9: new functions only;
  * pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in the reference, which
@@ -575,7 +635,9 @@ int pt_renderer_render_adaptive(pt_renderer *r, int first_iter, int min_iters, i
  * Unchanged: the primary-hit cache is still built once; pt_renderer_primary_hits, the
  * denoiser's guides and unjittered iterations read it.  Limit: the denoiser's guides are thus
  * the hit of the unjittered ray, so an anti-aliased edge pixel, a mix of two surfaces, is
- * filtered with the guides of one of them.  pt_renderer_segments counts a jittered iteration's
+ * filtered with the guides of one of them (flags without PT_DENOISE_SAMPLED_GUIDES; with
+ * pt_renderer_enable_guides and that flag the guides are the means over the jittered samples'
+ * own first hits).  pt_renderer_segments counts a jittered iteration's
  * generated rays as bounce 0 (the frame's launched pixels, as for masked iterations) and its
  * traced camera rays as bounce 1: the launched-pixel count more per iteration than
  * render_loop.  Jittered iterations are enqueued directly also under PT_GRAPH=1: never
@@ -626,7 +688,9 @@ typedef struct pt_camera {
  * float-representable (the default config's are).
  * The primary-hit cache is always the hit of the pinhole ray through the pixel's own point.
  * Limit: the denoiser's guides under a lens are thus the pinhole's, so a defocused pixel, a mix
- * of surfaces, is filtered with the guides of the surface its centre ray hits.
+ * of surfaces, is filtered with the guides of the surface its centre ray hits (flags without
+ * PT_DENOISE_SAMPLED_GUIDES; with pt_renderer_enable_guides and that flag the guides are the
+ * means over the lens samples' own first hits).
  * May be called before or after allocate_on_gpu.  After it the call is ordered on the renderer's
  * stream after everything enqueued (no synchronize is needed between render calls and view
  * changes; with PT_GRAPH=1 graphs in flight are waited for), invalidates the primary-hit cache,

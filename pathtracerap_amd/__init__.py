@@ -36,12 +36,14 @@ NOISE_TILE = 16     # PT_NOISE_TILE: Renderer.noise()'s tile edge in pixels
 DENOISE_MAX_PASSES = 6     # PT_DENOISE_MAX_PASSES
 DENOISE_DEMODULATE = 1     # PT_DENOISE_DEMODULATE (pt_renderer_denoise_ex's flags)
 DENOISE_TILE_COUNTS = 2    # PT_DENOISE_TILE_COUNTS
+DENOISE_SAMPLED_GUIDES = 4  # PT_DENOISE_SAMPLED_GUIDES
 
 
-def _denoise_flags(demodulate, tile_counts, flags):
+def _denoise_flags(demodulate, tile_counts, flags, sampled_guides=False):
     if flags is not None:
         return int(flags)
-    return (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TILE_COUNTS if tile_counts else 0)
+    return ((DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_TILE_COUNTS if tile_counts else 0) |
+            (DENOISE_SAMPLED_GUIDES if sampled_guides else 0))
 
 
 # renderer.h: segments[] slots after the per-bounce counters, as segments_per_bounce indices
@@ -168,6 +170,9 @@ EXPORTS = [
     ("pt_renderer_render_loop_masked", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_ubyte)]),
     ("pt_renderer_sample_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
+    ("pt_renderer_enable_guides", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    ("pt_renderer_read_guides", ctypes.c_int, [ctypes.c_void_p, _P_F]),
+    ("pt_renderer_guide_counts", ctypes.c_int, [ctypes.c_void_p, _P_I]),
     ("pt_renderer_adaptive_noise", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _P_F, _P_F]),
     ("pt_renderer_adaptive_mean", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _P_F]),
     ("pt_renderer_render_image_adaptive", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -760,6 +765,30 @@ class Renderer:
         _err(lib().pt_renderer_read_moments(self._h, _fp(out)), "read_moments")
         return out
 
+    def enable_guides(self, device_ptr: int | None = None, keepalive=None) -> None:
+        """Accumulate the first hit's features (normal, depth, sqrt albedo, hit flag) of every
+        jittered or lens sample beside the image and the moments (before allocateOnGPU; needs
+        enable_moments; include/pathtracer_amd.h, pt_renderer_enable_guides).  ``device_ptr``: a
+        caller-owned W*H*8 float buffer (a torch tensor, kept alive by ``keepalive``); None: the
+        renderer allocates it."""
+        self._guides_ref = keepalive
+        _err(lib().pt_renderer_enable_guides(self._h, ctypes.c_void_p(int(device_ptr)) if device_ptr else None),
+             "enable_guides")
+
+    def guides(self) -> dict:
+        """The sums G per pixel: ``normal`` (N, 3), ``depth`` (N,), ``sqrt_albedo`` (N, 3) and
+        ``hits`` (N,), float32; divide by ``hits`` for the means."""
+        g = np.zeros((self.cfg.width * self.cfg.height, 8), np.float32)
+        _err(lib().pt_renderer_read_guides(self._h, _fp(g)), "read_guides")
+        return dict(normal=g[:, 0:3].copy(), depth=g[:, 3].copy(), sqrt_albedo=g[:, 4:7].copy(), hits=g[:, 7].copy())
+
+    def guide_counts(self) -> np.ndarray:
+        """Samples per tile that accumulated guides since allocateOnGPU / clearImage,
+        (ceil(H/16), ceil(W/16)) int32."""
+        out = np.zeros(self._tiles(), np.int32)
+        _err(lib().pt_renderer_guide_counts(self._h, _ip(out)), "guide_counts")
+        return out
+
     def noise(self, samples: int | None = None) -> dict:
         """Relative noise estimate of the accumulated image (include/pathtracer_amd.h,
         pt_renderer_noise): ``mean`` over the frame, ``max_tile`` and the ``tiles``
@@ -782,7 +811,7 @@ class Renderer:
 
     def denoise(self, samples: int | None = None, passes: int = 5, sigma_l: float = 4.0, sigma_z: float = 1.0,
                 out_ptr: int | None = None, keepalive=None, variance: bool = False, demodulate: bool = False,
-                tile_counts: bool = False, flags: int | None = None):
+                tile_counts: bool = False, flags: int | None = None, sampled_guides: bool = False):
         """Variance-guided edge-avoiding filter of the accumulated mean image
         (include/pathtracer_amd.h, pt_renderer_denoise; needs enable_moments) -> the
         denoised (W*H, 3) float32 image, with ``variance=True`` (image, var (W*H,)).
@@ -792,34 +821,37 @@ class Renderer:
         ``keepalive``) that receives the image too.  The image and the moments are not
         modified.  ``demodulate``: filter the image divided by the primary hit's albedo and
         multiply it back (DENOISE_DEMODULATE); ``tile_counts``: divide by each tile's own
-        sample count, after masked or adaptive iterations (DENOISE_TILE_COUNTS); either
+        sample count, after masked or adaptive iterations (DENOISE_TILE_COUNTS);
+        ``sampled_guides``: guide the filter by the means of the samples' own first hits
+        (DENOISE_SAMPLED_GUIDES; needs enable_guides and jittered or lens iterations only); each
         goes through pt_renderer_denoise_ex, as does an explicit ``flags`` word."""
         self._denoise_ref = keepalive
         p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
         img = np.zeros((self.cfg.width * self.cfg.height, 3), np.float32)
         var = np.zeros(self.cfg.width * self.cfg.height, np.float32) if variance else None
         out = ctypes.c_void_p(int(out_ptr)) if out_ptr else None
-        if flags is None and not demodulate and not tile_counts:
+        if flags is None and not demodulate and not tile_counts and not sampled_guides:
             _err(lib().pt_renderer_denoise(self._h, int(samples or 0), ctypes.byref(p), out, _fp(img),
                                            _fp(var) if variance else None), "denoise")
         else:
             _err(lib().pt_renderer_denoise_ex(self._h, int(samples or 0), ctypes.byref(p),
-                                              _denoise_flags(demodulate, tile_counts, flags), out, _fp(img),
+                                              _denoise_flags(demodulate, tile_counts, flags, sampled_guides), out,
+                                              _fp(img),
                                               _fp(var) if variance else None), "denoise")
         return (img, var) if variance else img
 
     def renderImageDenoised(self, path: str = "Render.bmp", samples: int | None = None, passes: int = 5,
                             sigma_l: float = 4.0, sigma_z: float = 1.0, demodulate: bool = False,
-                            tile_counts: bool = False, flags: int | None = None) -> None:
+                            tile_counts: bool = False, flags: int | None = None, sampled_guides: bool = False) -> None:
         """The BMP of the denoised mean (renderImage's conversion of D * 255); ``demodulate``,
-        ``tile_counts`` and ``flags`` as for denoise()."""
+        ``tile_counts``, ``sampled_guides`` and ``flags`` as for denoise()."""
         p = _DenoiseParams(int(passes), float(sigma_l), float(sigma_z))
-        if flags is None and not demodulate and not tile_counts:
+        if flags is None and not demodulate and not tile_counts and not sampled_guides:
             _err(lib().pt_renderer_render_image_denoised(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p)),
                  "renderImageDenoised")
         else:
             _err(lib().pt_renderer_render_image_denoised_ex(self._h, os.fsencode(path), int(samples or 0), ctypes.byref(p),
-                                                            _denoise_flags(demodulate, tile_counts, flags)),
+                                                            _denoise_flags(demodulate, tile_counts, flags, sampled_guides)),
                  "renderImageDenoised")
 
     def denoise_times(self) -> dict:

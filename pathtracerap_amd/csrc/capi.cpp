@@ -424,6 +424,12 @@ int pt_renderer_denoise_times(pt_renderer* r, double* ms, int n) {
     if (!ms || n < 0) return set_err("bad arguments");
     R_CALL(r->r->denoiseTimes(ms, n));
 }
+int pt_renderer_enable_guides(pt_renderer* r, void* device_ptr) { R_CALL(r->r->enableGuides((float*)device_ptr)); }
+int pt_renderer_read_guides(pt_renderer* r, float* out) {
+    if (!out) return set_err("null buffer");
+    R_CALL(r->r->readGuides(out));
+}
+int pt_renderer_guide_counts(pt_renderer* r, int* tiles) { R_CALL(r->r->guideCounts(tiles)); }
 int pt_renderer_render_loop_masked(pt_renderer* r, int first_iter, int n_iters, const unsigned char* tile_mask_host) {
     R_CALL(r->r->renderLoopMasked(first_iter, n_iters, tile_mask_host));
 }

@@ -1,6 +1,7 @@
 // film.hip -- per-pixel second moment, noise estimate, render-until-converged, the
 // variance-guided edge-avoiding denoiser, and the host side of tile-masked sampling
-// with its per-tile estimate, mean and adaptive loop (no counterpart in the reference,
+// with its per-tile estimate, mean and adaptive loop, and the merge and the denoiser prep
+// of the sampled first-hit guides (no counterpart in the reference,
 // which renders a fixed ITER samples and writes the raw mean); and the host side of
 // environment lighting with its lookup test hook (pt_env.h), at the end.
 //
@@ -468,8 +469,195 @@ __global__ __launch_bounds__(256) void k_denoise_remod(float4* __restrict__ cv, 
 }
 
 // ---------------------------------------------------------------------------
+// Sampled first-hit guides (pt_renderer_enable_guides, PT_DENOISE_SAMPLED_GUIDES): G holds per
+// pixel the sums (Nx, Ny, Nz, Z, Ar, Ag, Ab, Hc) of the records k_guide_first (renderer.hip)
+// wrote for the generated iterations; the guided prep reads their means where the plain one
+// reads the primary-hit cache.  tests/guides_ref.py restates both bit for bit.
+// ---------------------------------------------------------------------------
+
+// Whether pixel px lies in a tile the mask keeps (null: every tile).
+__device__ inline bool dn_tile_on(const unsigned char* __restrict__ tile_mask, int tiles_x, int W, size_t px) {
+    if (!tile_mask) return true;
+    const int y = (int)(px / (size_t)W), x = (int)(px - (size_t)y * W);
+    return tile_mask[(y / kTile) * tiles_x + (x / kTile)] != 0;
+}
+
+// G += one generated iteration's records, n = W*H pixels of 8 floats, one add per float.
+// Memory bound (one stream read-modify-write, one read): VEC moves 16 bytes per lane, two
+// lanes per pixel, and needs a 16-byte aligned G (rec is the renderer's own allocation); a
+// caller-bound G with less alignment takes the scalar variant, as in k_merge_m2.  Under a tile
+// mask (a kernel argument: wave-uniform) only the pixels of active tiles are added: the
+// pipeline's buffer still holds an earlier iteration's records for the others.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_merge_guides(float* __restrict__ G, const float* __restrict__ rec, size_t n,
+                                                      const unsigned char* __restrict__ tile_mask, int tiles_x, int W) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        if (i >= 2 * n || !dn_tile_on(tile_mask, tiles_x, W, i >> 1)) return;
+        const float4 c = reinterpret_cast<const float4*>(rec)[i];
+        float4 g = reinterpret_cast<float4*>(G)[i];
+        g.x += c.x; g.y += c.y; g.z += c.z; g.w += c.w;
+        reinterpret_cast<float4*>(G)[i] = g;
+    } else {
+        if (i >= 8 * n || !dn_tile_on(tile_mask, tiles_x, W, i >> 3)) return;
+        G[i] += rec[i];
+    }
+}
+
+// Pixel p's record of G.  vec (a kernel argument: wave-uniform): G is 16-byte aligned, two
+// 16-byte loads; else eight 4-byte loads (a caller-bound G).
+__device__ inline void dn_guide_load(const float* __restrict__ G, size_t p, bool vec, float* g) {
+    if (vec) {
+        const float4 a = reinterpret_cast<const float4*>(G)[2 * p], b = reinterpret_cast<const float4*>(G)[2 * p + 1];
+        g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+    } else {
+        for (int k = 0; k < 8; k++) g[k] = G[8 * p + k];
+    }
+}
+
+// Depth of frame pixel (x, y) from the sums: Z / Hc, FLT_MAX where no sample hit.
+__device__ inline float dn_guide_depth(const float* __restrict__ G, int W, int x, int y) {
+    const float* g = G + 8 * ((size_t)y * W + x);
+    const float h = g[7];
+    return h > 0.0f ? g[3] / h : FLT_MAX;
+}
+
+// The sampled sqrt-space albedo of a pixel with sums a (Ar, Ag, Ab) and Hc = h over nf samples:
+// a sample that missed counts as albedo 1.  The sum is rounded before the division.
+__device__ inline void dn_guide_albedo(const float* a, float h, float nf, float* sa, float* e) {
+    for (int c = 0; c < 3; c++) {
+        sa[c] = (a[c] + (nf - h)) / nf;
+        e[c] = sa[c] > 1e-3f ? sa[c] : 1e-3f;
+    }
+}
+
+// pt_renderer_denoise_ex with PT_DENOISE_SAMPLED_GUIDES: k_denoise_prep's records from G in place
+// of the primary-hit cache.  One pixel per lane: 24 bytes of S and Q, the pixel's 32-byte record
+// and (Z, Hc) of its four neighbours.  model = 0 where a sample hit, -1 elsewhere, so the passes'
+// model test is "both pixels saw a surface"; the normal is the mean one, not renormalised.
+template <bool DEMOD, bool COUNTS>
+__global__ __launch_bounds__(256) void k_denoise_prep_guided(const float* __restrict__ S, const float* __restrict__ Q,
+                                                             float nf, const float* __restrict__ G, int W, int H,
+                                                             float4* __restrict__ cv, float4* __restrict__ nd,
+                                                             int* __restrict__ model, float* __restrict__ slope,
+                                                             const int* __restrict__ counts, int tiles_x, bool vec) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (size_t)W * H) return;
+    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+    if (COUNTS) nf = (float)counts[(y / kTile) * tiles_x + (x / kTile)];
+    float g[8];
+    dn_guide_load(G, p, vec, g);
+    const float h = g[7];
+    float m[3], v[3];
+    for (int k = 0; k < 3; k++) {
+        m[k] = S[3 * p + k] / nf;
+        const float qq = Q[3 * p + k] / nf;
+        float t = qq - m[k] * m[k];
+        t = t > 0.0f ? t : 0.0f;
+        v[k] = t / (nf - 1.0f);
+    }
+    if (DEMOD) {
+        float sa[3], e[3];
+        dn_guide_albedo(g + 4, h, nf, sa, e);
+        for (int k = 0; k < 3; k++) {
+            m[k] = m[k] / e[k];
+            v[k] = v[k] / (e[k] * e[k]);
+        }
+    }
+    cv[p] = make_float4(m[0], m[1], m[2], (v[0] + v[1]) + v[2]);
+    const bool hit = h > 0.0f;
+    nd[p] = hit ? make_float4(g[0] / h, g[1] / h, g[2] / h, g[3] / h) : make_float4(0.0f, 0.0f, 0.0f, FLT_MAX);
+    model[p] = hit ? 0 : -1;
+    const int xm = dn_clamp(x - 1, W - 1), xp = dn_clamp(x + 1, W - 1);
+    const int ym = dn_clamp(y - 1, H - 1), yp = dn_clamp(y + 1, H - 1);
+    const float gx = fabsf(dn_guide_depth(G, W, xp, y) - dn_guide_depth(G, W, xm, y)) * 0.5f;
+    const float gy = fabsf(dn_guide_depth(G, W, x, yp) - dn_guide_depth(G, W, x, ym)) * 0.5f;
+    slope[p] = gx > gy ? gx : gy;
+}
+
+// k_denoise_remod for the guided prep: D = c * sa with prep's sampled sa, recomputed from G and
+// the same nf by the same expression (so it is prep's value), also for a pixel no sample hit
+// (sa = 1: it keeps its bits).
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_denoise_remod_guided(float4* __restrict__ cv, const float* __restrict__ G,
+                                                              size_t n, float nf, int W, const int* __restrict__ counts,
+                                                              int tiles_x, bool vec) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (COUNTS) {
+        const int y = (int)(i / (size_t)W), x = (int)(i - (size_t)y * W);
+        nf = (float)counts[(y / kTile) * tiles_x + (x / kTile)];
+    }
+    float g[8];
+    dn_guide_load(G, i, vec, g);
+    float sa[3], e[3];
+    dn_guide_albedo(g + 4, g[7], nf, sa, e);
+    float4 c = cv[i];
+    c.x = c.x * sa[0]; c.y = c.y * sa[1]; c.z = c.z * sa[2];
+    cv[i] = c;
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
+int Renderer::enableGuides(float* device_g) {
+    if (allocated) { last_error = "enable_guides must precede allocateOnGPU"; return -1; }
+    guides_on = true;
+    ext_guides = device_g;
+    return 0;
+}
+
+// allocateOnGPU: G (unless the caller owns it) and one record buffer per pipeline, zeroed: a
+// pixel that never emits a ray (tail_drop) contributes zeros.
+int Renderer::allocGuides() {
+    const size_t bytes = (size_t)cfg.width * cfg.height * 8 * sizeof(float);
+    void* d = nullptr;
+    if (ext_guides) {
+        guides = ext_guides;
+    } else {
+        PT_HIP(hipMalloc(&d, bytes));
+        allocs.push_back(d);
+        guides = (float*)d;
+    }
+    for (int i = 0; i < npipes; i++) {
+        PT_HIP(hipMalloc(&d, bytes));
+        allocs.push_back(d);
+        guide_contrib[i] = (float*)d;
+        PT_HIP(hipMemsetAsync(d, 0, bytes, stream));
+    }
+    return 0;
+}
+
+// G += pipeline q's records on its stream st, right after launchMergeM2: the same place in the
+// ordered merge chain, so the sums do not depend on the pipeline count.
+int Renderer::launchMergeGuides(int q, hipStream_t st, const unsigned char* tile_mask) {
+    const size_t n = (size_t)cfg.width * cfg.height;
+    const int tx = noiseTilesX();
+    if (((uintptr_t)guides & 15) == 0)
+        hipLaunchKernelGGL(k_merge_guides<true>, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, guides,
+                           guide_contrib[q], n, tile_mask, tx, cfg.width);
+    else
+        hipLaunchKernelGGL(k_merge_guides<false>, dim3((unsigned)((8 * n + 255) / 256)), dim3(256), 0, st, guides,
+                           guide_contrib[q], n, tile_mask, tx, cfg.width);
+    PT_HIP(hipGetLastError());
+    return 0;
+}
+
+int Renderer::readGuides(float* host_g) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!guides_on) { last_error = "guides not enabled"; return -1; }
+    PT_HIP(hipMemcpyAsync(host_g, guides, (size_t)cfg.width * cfg.height * 8 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    PT_HIP(hipStreamSynchronize(stream));
+    return checkFaults();
+}
+
+int Renderer::guideCounts(int* tile_counts_host) {
+    if (!allocated) { last_error = "not allocated"; return -1; }
+    if (!guides_on) { last_error = "guides not enabled"; return -1; }
+    if (tile_counts_host) std::copy(guide_tile_counts.begin(), guide_tile_counts.end(), tile_counts_host);
+    return (int)guide_tile_counts.size();
+}
+
 int Renderer::enableMoments(float* device_m2) {
     if (allocated) { last_error = "enable_moments must precede allocateOnGPU"; return -1; }
     moments_on = true;
@@ -644,7 +832,18 @@ int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, i
     if (!allocated) { last_error = "not allocated"; return -1; }
     if (!moments_on) { last_error = "moments not enabled"; return -1; }
     const bool demod = (flags & PT_DENOISE_DEMODULATE) != 0, by_tile = (flags & PT_DENOISE_TILE_COUNTS) != 0;
-    if (flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_TILE_COUNTS)) { last_error = "denoise_ex: unknown flag bits"; return -1; }
+    const bool guided = (flags & PT_DENOISE_SAMPLED_GUIDES) != 0;
+    const bool vouched = samples > 0;        // an explicit count: the caller vouches that every sample left a record
+    if (flags & ~(PT_DENOISE_DEMODULATE | PT_DENOISE_TILE_COUNTS | PT_DENOISE_SAMPLED_GUIDES)) {
+        last_error = "denoise_ex: unknown flag bits";
+        return -1;
+    }
+    // without pt_renderer_enable_guides the bit is as unknown to this renderer as it was before guides existed
+    if (guided && !guides_on) {
+        last_error = "denoise_ex: unknown flag bits (PT_DENOISE_SAMPLED_GUIDES: guides not enabled; call "
+                     "pt_renderer_enable_guides before allocate_on_gpu)";
+        return -1;
+    }
     if (by_tile && samples > 0) {
         last_error = "denoise_ex: PT_DENOISE_TILE_COUNTS takes every tile's own sample count; samples must be <= 0";
         return -1;
@@ -661,6 +860,11 @@ int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, i
         if (samples <= 0) samples = samples_accumulated;
         if (samples < 2) { last_error = "need at least 2 samples"; return -1; }
     }
+    if (guided && !vouched && guide_tile_counts != tile_counts) {
+        last_error = "denoise_ex: PT_DENOISE_SAMPLED_GUIDES: a tile's guide count differs from its sample count; every "
+                     "sample since the last clear must be a generated (jittered or lens) iteration, or pass samples > 0";
+        return -1;
+    }
     if (passes < 1 || passes > PT_DENOISE_MAX_PASSES || !std::isfinite(sigma_l) || !(sigma_l > 0.0f) ||
         !std::isfinite(sigma_z) || !(sigma_z > 0.0f)) {
         last_error = "bad denoise parameters";
@@ -676,7 +880,7 @@ int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, i
         }
     }
     if (allocDenoise() != 0) return -1;
-    if (!cache_valid && launchPrimary() != 0) return -1;
+    if (!guided && !cache_valid && launchPrimary() != 0) return -1;     // the guided prep reads G, not the cache
     if (by_tile && uploadTileCounts() != 0) return -1;
     const int W = cfg.width, H = cfg.height;
     const size_t n = (size_t)W * H;
@@ -699,7 +903,18 @@ int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, i
     const DnPrepOpt opt = {demod ? kp.cache_albedo : nullptr, demod ? kp.shade : nullptr,
                            by_tile ? tile_counts_dev : nullptr, tx};
     const bool vec = (((uintptr_t)kp.image | (uintptr_t)m2) & 15) == 0;
-    if (vec) {
+    const bool gvec = ((uintptr_t)guides & 15) == 0;
+    const dim3 gpix((unsigned)((n + 255) / 256));
+    if (guided) {
+#define PT_PREP_G(D, C) \
+    hipLaunchKernelGGL((k_denoise_prep_guided<D, C>), gpix, dim3(256), 0, stream, kp.image, m2, (float)samples, guides, W, H, \
+                       dn_cv[0], dn_nd, dn_model, dn_slope, opt.counts, tx, gvec)
+        if (demod && by_tile) PT_PREP_G(true, true);
+        else if (demod) PT_PREP_G(true, false);
+        else if (by_tile) PT_PREP_G(false, true);
+        else PT_PREP_G(false, false);
+#undef PT_PREP_G
+    } else if (vec) {
         const size_t n4 = n >> 2;
         launchDenoisePrep<true>(flags, dim3((unsigned)std::max<size_t>(1, (n4 + 255) / 256)), stream, kp.image, m2,
                                 (float)samples, kp.cache_hit, kp.cache_model, kp.npix, W, H, dn_cv[0], dn_nd, dn_model,
@@ -730,8 +945,15 @@ int Renderer::denoiseEx(int samples, int passes, float sigma_l, float sigma_z, i
     dn_event_passes = timed ? passes : 0;
     float4* result = dn_cv[passes & 1];
     if (demod) {
-        hipLaunchKernelGGL(k_denoise_remod, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, result, dn_model, n,
-                           kp.cache_albedo, kp.shade);
+        if (guided && by_tile)
+            hipLaunchKernelGGL(k_denoise_remod_guided<true>, gpix, dim3(256), 0, stream, result, guides, n, (float)samples,
+                               W, opt.counts, tx, gvec);
+        else if (guided)
+            hipLaunchKernelGGL(k_denoise_remod_guided<false>, gpix, dim3(256), 0, stream, result, guides, n, (float)samples,
+                               W, opt.counts, tx, gvec);
+        else
+            hipLaunchKernelGGL(k_denoise_remod, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, result, dn_model, n,
+                               kp.cache_albedo, kp.shade);
         PT_HIP(hipGetLastError());
         if (mark() != 0) return -1;
         dn_event_remod = timed;
@@ -865,8 +1087,12 @@ int Renderer::renderLoopMasked(int first_iter, int n_iters, const unsigned char*
     mask_slot = (mask_slot + 1) % kMaskSlots;
     int done = 0;
     const int rc = renderIters(first_iter, n_iters, tile_mask_dev, &done);
+    const bool gen = guides_on && generatedIterations();
     for (size_t t = 0; t < nt; t++)
-        if (stage[t]) tile_counts[t] += done;
+        if (stage[t]) {
+            tile_counts[t] += done;
+            if (gen) guide_tile_counts[t] += done;
+        }
     return rc;
 }
 

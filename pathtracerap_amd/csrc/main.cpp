@@ -3,7 +3,7 @@
 //
 //   pathtracer_amd <scene.txt> [out.bmp] [--res W H] [--iter N] [--bounces B] [--grid|--grid-fast|--bvh]
 //                  [--pipelines P] [--noise-target X [--check-every N]] [--denoise [--denoise-passes N]]
-//                  [--denoise-albedo] [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
+//                  [--denoise-albedo] [--denoise-guides] [--adaptive X [--check-every N] [--min-iter N]] [--jitter WIDTH]
 //                  [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] [--focus D] [--lens R]]
 //                  [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]
 //
@@ -39,7 +39,9 @@
 // (pt_renderer_render_image_denoised over the iterations actually rendered, N a-trous
 // passes, default 5) instead of the raw mean.  --denoise-albedo implies --denoise and filters the
 // image with the primary hit's albedo divided out (pt_renderer_render_image_denoised_ex with
-// PT_DENOISE_DEMODULATE), so a texture is not blurred.
+// PT_DENOISE_DEMODULATE), so a texture is not blurred.  --denoise-guides implies --denoise too:
+// the filter's guides are the means of the samples' own first hits (pt_renderer_enable_guides,
+// PT_DENOISE_SAMPLED_GUIDES); it needs --jitter or a lens, whose iterations accumulate them.
 //
 // Default: PT_ACCEL_GRID_FAST (the reference grid's image, bit for bit) with 16
 // iterations in flight, each on its own HIP stream and hardware queue.
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s scene.txt [out.bmp] [--res W H] [--iter N] [--bounces B] "
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
-                             "[--denoise [--denoise-passes N]] [--denoise-albedo] [--adaptive X [--check-every N] [--min-iter N]] "
+                             "[--denoise [--denoise-passes N]] [--denoise-albedo] [--denoise-guides] [--adaptive X [--check-every N] [--min-iter N]] "
                              "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
                              "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]\n", argv[0]);
         return 2;
@@ -109,6 +111,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--smooth")) smooth = true;
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-albedo")) { denoise = true; denoise_flags |= PT_DENOISE_DEMODULATE; }
+        else if (!std::strcmp(argv[i], "--denoise-guides")) { denoise = true; denoise_flags |= PT_DENOISE_SAMPLED_GUIDES; }
         else if (!std::strcmp(argv[i], "--denoise-passes") && i + 1 < argc) dn.passes = std::atoi(argv[++i]);
         else out = argv[i];
     }
@@ -137,10 +140,16 @@ int main(int argc, char** argv) {
         has_cam = pt_scene_camera(s, cfg.width, cfg.height, &cam);
     }
     if (has_cam < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
+    const bool guides = (denoise_flags & PT_DENOISE_SAMPLED_GUIDES) != 0;
+    if (guides && !jitter && !(has_cam > 0 && cam.lens_radius > 0.0f)) {
+        std::fprintf(stderr, "--denoise-guides needs --jitter or a lens (--lens R): only their iterations accumulate guides\n");
+        return 2;
+    }
     if (smooth && pt_scene_set_model_smooth(s, -1, 1) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
-    if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
+    if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) ||
+        (guides && pt_renderer_enable_guides(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }

@@ -238,6 +238,13 @@ public:
     // test hook: the albedo definition evaluated on the device for caller-given hits
     int hitAlbedo(int n, const float* orig, const float* dir, const float* dist, const int* model, const int* tri,
                   float* rgb_out);
+    // Sampled first-hit guides (film.hip; no counterpart in the reference): per pixel the sums G of
+    // the first hit's (normal, depth, sqrt albedo, hit flag) over the generated (jittered or lens)
+    // iterations, accumulated beside the image and the moments; PT_DENOISE_SAMPLED_GUIDES makes the
+    // denoiser's prep read their means in place of the primary-hit cache
+    int enableGuides(float* device_g);               // before allocateOnGPU; null: own buffer
+    int readGuides(float* host_g);                   // W*H*8 floats
+    int guideCounts(int* tile_counts_host);          // returns the tile count
 
     RenderConfig cfg;
     std::string last_error;
@@ -266,6 +273,12 @@ private:
     int checkFaults();
     int allocMoments();
     int launchMergeM2(const KParams& k, hipStream_t st);
+    int allocGuides();
+    bool splitTraceWanted() const;
+    // the iterations enqueued now generate their camera rays (k_gen_jitter / k_gen_camera)
+    bool generatedIterations() const { return jitter_on || (camera_on && cam_rec.lens_radius > 0.0f); }
+    int launchGuideFirst(const KParams& k, int q, hipStream_t st);
+    int launchMergeGuides(int q, hipStream_t st, const unsigned char* tile_mask);
     int allocDenoise();
     int writeBmp(const std::string& path, const float* rgb, float div);     // Renderer.cpp:15-63
 
@@ -291,6 +304,11 @@ private:
     bool moments_on = false;         // enableMoments: every pipeline has a contribution buffer, k_merge_m2 merges
     float* ext_m2 = nullptr;         // the caller's moment buffer (null: allocated here)
     float* m2 = nullptr;             // W*H*3 sums of squared contributions
+    bool guides_on = false;          // enableGuides: generated iterations accumulate first-hit guides
+    float* ext_guides = nullptr;     // the caller's guide buffer (null: allocated here)
+    float* guides = nullptr;         // W*H*8 sums G
+    float* guide_contrib[kMaxPipes]{};   // pipeline i's per-iteration records (k_guide_first -> k_merge_guides)
+    std::vector<int> guide_tile_counts;  // generated samples per noise tile since allocateOnGPU / clearImage (host)
     double* noise_sum = nullptr;     // noise(): per-tile sums, then the mean
     float* noise_err = nullptr;      // per-tile errors, then the largest
     int samples_accumulated = 0;     // iterations enqueued since allocateOnGPU / clearImage

@@ -3284,6 +3284,36 @@ __global__ void k_zero(float* a, size_t n) {
     if (i < n) a[i] = 0.0f;
 }
 
+// Sampled first-hit guides (pt_renderer_enable_guides): the record of every ray a generated
+// iteration emitted, from pass 1's hit buffer, after that pass's trace and before its shading
+// pass and scan move on.  One lane per live slot j of pass 1 (n_live[1]: every emitted ray);
+// the slot's ray is found as k_bounce<rest, hitbuf> finds it (slot_src when the pass was
+// sorted, else the blk_off search) in pool 0, where the generating kernel left it.  A hit
+// writes (n, t, sqrt(pos(albedo)), 1) with the normal and the albedo the shading pass uses, a
+// miss eight zeros, as two 16-byte stores at the ray's pixel in this pipeline's record buffer
+// (W*H*8 floats), which k_merge_guides then adds to G.  Reads 36 + 20 bytes per ray and the
+// hit's triangle and model records; no atomics.
+// (Defined after every other kernel, so that the kernels before it keep their places in the code object.)
+__global__ __launch_bounds__(256) void k_guide_first(KParams p, float* __restrict__ rec) {
+    const int n = p.n_live[1];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int src = p.slot_src ? p.slot_src[j] : slot_source(p, j);
+    const RayState r = load_ray<2>(p, 0, src);
+    if ((unsigned)r.pixel >= (unsigned)p.npix) return;      // never: the generating kernel wrote a launched pixel
+    const Hit h = p.smooth ? get_hit(p, j, r.o, r.d) : get_hit(p, j);     // a kernel argument: wave-uniform
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (h.model >= 0) {
+        const f3 mc = hit_albedo(p, r.o, r.d, h.dist, h.model, __float_as_int(p.hit4[j].y));
+        a = make_float4(h.n.x, h.n.y, h.n.z, h.dist);
+        b = make_float4(sqrtf(mc.x > 0.0f ? mc.x : 0.0f), sqrtf(mc.y > 0.0f ? mc.y : 0.0f),
+                        sqrtf(mc.z > 0.0f ? mc.z : 0.0f), 1.0f);
+    }
+    float4* dst = reinterpret_cast<float4*>(rec) + 2 * (size_t)r.pixel;
+    dst[0] = a;
+    dst[1] = b;
+}
+
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
@@ -3339,6 +3369,15 @@ static hipError_t upload(std::vector<void*>& allocs, T** dst, const void* src, s
     return e;
 }
 
+// Persistent trace + shading pass; PT_TRACE_SPLIT=0 / PT_GF_SPLIT=0 keep the fused kernel.
+bool Renderer::splitTraceWanted() const {
+    const char* e = std::getenv("PT_TRACE_SPLIT");
+    bool split = cfg.accel == ACCEL_BVH && !(e && std::atoi(e) == 0);
+    const char* eg = std::getenv("PT_GF_SPLIT");
+    if (cfg.accel == ACCEL_GRID_FAST) split = eg ? std::atoi(eg) != 0 : true;
+    return split;
+}
+
 int Renderer::allocateOnGPU(const Scene& scene) {
     if (!scene.built) { last_error = "scene not built (call build first)"; return -1; }
     if (cfg.width <= 0 || cfg.height <= 0) { last_error = "bad resolution"; return -1; }
@@ -3357,6 +3396,15 @@ int Renderer::allocateOnGPU(const Scene& scene) {
             }
     for (const Voxel& v : scene.voxels)
         if (v.entity_type != ENTITY_TRIANGLE) { last_error = "unsupported voxel entity type"; return -1; }
+    if (guides_on && !moments_on) {
+        last_error = "guides need moments (call pt_renderer_enable_moments before allocate_on_gpu too)";
+        return -1;
+    }
+    if (guides_on && !splitTraceWanted()) {
+        last_error = "guides need the split trace, whose hit records they read: ACCEL_GRID_FAST or ACCEL_BVH without "
+                     "PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0";
+        return -1;
+    }
     freeBuffers();
     if (!stream_set && !stream) {
         PT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -3498,11 +3546,7 @@ int Renderer::allocateOnGPU(const Scene& scene) {
         kp.hs_pool_blocks = cfg.accel == ACCEL_GRID_FAST ? (hpb ? std::max(1, std::atoi(hpb)) : 65536) : 1;   // 64 MiB
     }
     {
-        // Persistent trace + shading pass; PT_TRACE_SPLIT=0 / PT_GF_SPLIT=0 keep the fused kernel.
-        const char* e = std::getenv("PT_TRACE_SPLIT");
-        split_trace = cfg.accel == ACCEL_BVH && !(e && std::atoi(e) == 0);
-        const char* eg = std::getenv("PT_GF_SPLIT");
-        if (cfg.accel == ACCEL_GRID_FAST) split_trace = eg ? std::atoi(eg) != 0 : true;
+        split_trace = splitTraceWanted();
         // trace variants: 9 / 11 model records in LDS (the default), 8 / 10 from global memory
         const char* gff = std::getenv("PT_GF_FLAGS");
         // each flag is checked only where it applies (split grid_fast / split bvh): a leftover
@@ -3627,6 +3671,7 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     if (!fork_ev) PT_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
     kp = pk[0];
     if (moments_on && allocMoments() != 0) return -1;
+    if (guides_on && allocGuides() != 0) return -1;
     PT_HIP(hipStreamSynchronize(stream));
     const char* gr = std::getenv("PT_GRAPH");
     use_graph = gr && std::atoi(gr) != 0;
@@ -3699,8 +3744,14 @@ int Renderer::clearImage() {
         hipLaunchKernelGGL(k_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m2, n);
         PT_HIP(hipGetLastError());
     }
+    if (guides_on) {
+        const size_t n8 = (size_t)cfg.width * cfg.height * 8;
+        hipLaunchKernelGGL(k_zero, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, guides, n8);
+        PT_HIP(hipGetLastError());
+    }
     samples_accumulated = 0;
     tile_counts.assign((size_t)noiseTilesX() * noiseTilesY(), 0);
+    guide_tile_counts.assign(tile_counts.size(), 0);
     // a fault invalidated the image it was counted against; the cleared image starts
     // a new render, so later checks report only faults of renders after this point
     PT_HIP(hipMemsetAsync(kp.segments + kTraceFaultCounter, 0, sizeof(unsigned long long), stream));
@@ -3911,6 +3962,14 @@ int Renderer::pixelJitter(int* on, float* width) const {
     return 0;
 }
 
+// k_guide_first over pass 1's slots on pipeline q (k: the parameters that pass ran with, its
+// slot map or none); one lane per launched pixel, the lanes beyond n_live[1] leave at once.
+int Renderer::launchGuideFirst(const KParams& k, int q, hipStream_t st) {
+    hipLaunchKernelGGL(k_guide_first, dim3((unsigned)((k.npix + 255) / 256)), dim3(256), 0, st, k, guide_contrib[q]);
+    PT_HIP(hipGetLastError());
+    return 0;
+}
+
 // Bounce b's ray sort (when the pipeline sorts) and persistent trace launches, as
 // every iteration enqueues them (and the trace_rays test hook).  pall / ptrace: an
 // event pair around the sort kernels / around the trace launches only.  host_rays: the
@@ -3967,6 +4026,9 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, cons
             KParams ku = k;
             if (unsorted) { ku.order = nullptr; ku.slot_src = nullptr; }
             if (enqueueSortTrace(ku, st, b, pall, ptrace, false) != 0) return -1;
+            // sampled guides: pass 1's hit records, before its shading pass writes pool 1 and its
+            // scan the offsets (outside the event pairs: the kernel groups keep their meaning)
+            if (b == 1 && jitter && guides_on && launchGuideFirst(ku, q, st) != 0) return -1;
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             launchBounce(ku, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
@@ -4003,6 +4065,8 @@ int Renderer::renderLoop(int first_iter, int n_iters) {
     int done = 0;
     const int rc = renderIters(first_iter, n_iters, nullptr, &done);
     for (int& c : tile_counts) c += done;            // every tile: host only
+    if (guides_on && generatedIterations())
+        for (int& c : guide_tile_counts) c += done;
     return rc;
 }
 
@@ -4031,7 +4095,7 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
     // jittered iterations are enqueued directly, like masked ones: never captured, never
     // replayed, so the graphs of the plain loop stay valid across a switch
     // ... and so are the iterations through a lens, whose rays are generated too
-    const bool jitter = jitter_on || (camera_on && cam_rec.lens_radius > 0.0f);
+    const bool jitter = generatedIterations();
     const int np = npipes;
     if (np > 1) {                                   // fork the pipeline streams off the caller's stream
         PT_HIP(hipEventRecord(fork_ev, stream));
@@ -4072,6 +4136,7 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
             if (it > 0) PT_HIP(hipStreamWaitEvent(st, merge_ev[(it - 1) % np], 0));
             if (moments_on) {
                 if (launchMergeM2(k, st) != 0) return -1;    // ... and m2 += their squares, in the same pass
+                if (jitter && guides_on && launchMergeGuides(q, st, tile_mask) != 0) return -1;   // ... and G += its records
             } else {
                 hipLaunchKernelGGL(k_merge, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, k.image, k.contrib, n3);
                 PT_HIP(hipGetLastError());
@@ -4081,6 +4146,7 @@ int Renderer::renderIters(int first_iter, int n_iters, const unsigned char* tile
             // one pipeline: k_bounce wrote the contribution buffer instead of the image;
             // the same single add per pixel, on the same stream
             if (launchMergeM2(k, st) != 0) return -1;
+            if (jitter && guides_on && launchMergeGuides(q, st, tile_mask) != 0) return -1;
         }
         return 0;
     };
@@ -4484,6 +4550,8 @@ void Renderer::freeBuffers() {
     allocs.clear();
     kp.image = nullptr;
     m2 = nullptr;
+    guides = nullptr;
+    for (int i = 0; i < kMaxPipes; i++) guide_contrib[i] = nullptr;
     noise_sum = nullptr;
     noise_err = nullptr;
     dn_cv[0] = dn_cv[1] = dn_nd = nullptr;

@@ -28,7 +28,7 @@ def shard_iterations(total: int, rank: int, world: int) -> tuple[int, int]:
 
 def render_sharded(scene, cfg, total_iters: int, device=None,
                    render_fn: Optional[Callable] = None, moments: bool = False,
-                   jitter: Optional[float] = None, camera=None, environment=None):
+                   jitter: Optional[float] = None, camera=None, environment=None, guides: bool = False):
     """Render ``total_iters`` samples per pixel across the process group and
     return the summed accumulator (a (W*H*3,) float32 tensor on every rank).
 
@@ -42,6 +42,12 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
     ``Renderer.noise(total_iters)`` on the reduced buffers.  ``render_fn`` is
     then called as ``render_fn(first, n, image_tensor, m2_tensor)`` and
     ``noise`` is None.
+
+    ``guides=True`` (needs ``moments=True`` and generated iterations: ``jitter`` or a lens)
+    also accumulates the sampled first-hit guides (Renderer.enable_guides) in a third tensor of
+    W*H*8 floats; the sums are additive over iteration shards like the other two, so it is
+    all-reduced beside them and returned after ``m2``: ``(image, m2, guides, noise)``.
+    ``render_fn`` is then called as ``render_fn(first, n, image_tensor, m2_tensor, guides_tensor)``.
 
     ``jitter``: a width turns on pixel-jittered camera rays (Renderer.set_pixel_jitter)
     on every rank; the offset depends on (iteration, pixel) only, so the shards add up
@@ -66,8 +72,13 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
         device = torch.device("cuda", torch.cuda.current_device()) if render_fn is None else torch.device("cpu")
     image = torch.zeros(cfg.width * cfg.height * 3, dtype=torch.float32, device=device)
     m2 = torch.zeros_like(image) if moments else None
+    if guides and not moments:
+        raise ValueError("render_sharded: guides=True needs moments=True")
+    g = torch.zeros(cfg.width * cfg.height * 8, dtype=torch.float32, device=device) if guides else None
     if render_fn is not None:
-        if moments:
+        if guides:
+            render_fn(first, n, image, m2, g)
+        elif moments:
             render_fn(first, n, image, m2)
         else:
             render_fn(first, n, image)
@@ -78,6 +89,8 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
         r.bind_image(image.data_ptr(), keepalive=image)
         if moments:
             r.enable_moments(m2.data_ptr(), keepalive=m2)
+        if guides:
+            r.enable_guides(g.data_ptr(), keepalive=g)
         if jitter is not None:
             r.set_pixel_jitter(jitter)
         if camera is not None:
@@ -90,10 +103,14 @@ def render_sharded(scene, cfg, total_iters: int, device=None,
         dist.all_reduce(image, op=dist.ReduceOp.SUM)      # RCCL (nccl backend) over xGMI, or gloo
         if moments:
             dist.all_reduce(m2, op=dist.ReduceOp.SUM)
+        if guides:
+            dist.all_reduce(g, op=dist.ReduceOp.SUM)
     noise = None
     if render_fn is None:
         torch.cuda.synchronize(device)
         if moments:
             noise = r.noise(total_iters)      # on the reduced image and moments, before they are unbound
         r.free()
+    if guides:
+        return image, m2, g, noise
     return (image, m2, noise) if moments else image
