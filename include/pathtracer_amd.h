@@ -40,7 +40,8 @@ extern "C" {
 /* Primitive.h:70-79 Material::MaterialType */
 enum {
     PT_MAT_DIFFUSE = 0, PT_MAT_SPECULAR = 1, PT_MAT_REFLECTIVE = 2, PT_MAT_REFRACTIVE = 3,
-    PT_MAT_EMISSIVE = 4, PT_MAT_COAT = 5, PT_MAT_METAL = 6
+    PT_MAT_EMISSIVE = 4, PT_MAT_COAT = 5, PT_MAT_METAL = 6,
+    PT_MAT_DIELECTRIC = 7   /* glass; not the reference's: see "Dielectric material" below */
 };
 
 /* Intersect-stage acceleration structure. */
@@ -218,6 +219,60 @@ int pt_scene_texture_count(const pt_scene *s);
 int pt_scene_texture(const pt_scene *s, int texture, int *w, int *h, float *rgb_out);
 int pt_scene_set_model_texture(pt_scene *s, int model, int texture);
 int pt_scene_model_texture(const pt_scene *s, int model);
+/* ---- Dielectric material: refraction, Fresnel reflection and total internal reflection (added
+ * within ABI 9: one new material value and new functions only; pt_scene_add_model's signature,
+ * pt_render_config and PT_ABI_VERSION are unchanged.  No counterpart in the reference, whose
+ * shading has no branch for its SPECULAR and REFRACTIVE types: those two keep doing what they
+ * did, a hit only loses a bounce).  Off by default: a scene without a PT_MAT_DIELECTRIC model
+ * allocates, launches and computes exactly what it did. ----
+ * pt_scene_add_model accepts material PT_MAT_DIELECTRIC (7); a value above 7 is refused as before
+ * ("addModel: bad material").  pt_scene_set_model_ior stores the index of refraction of one model;
+ * model = -1: of every model added so far.  It is stored for every model and read only by a
+ * dielectric one; 1.5 by default.  Before or after pt_scene_build: the grid and the BLAS are not
+ * touched.  pt_renderer_allocate_on_gpu snapshots the values with the materials: a change made
+ * afterwards applies to the next allocation.  Refused: "setModelIor: bad model index",
+ * "setModelIor: ior must be finite and in [1, 4]".  pt_scene_model_ior reads it back; a negative
+ * value: error ("pt_scene_model_ior: bad model index").
+ * Definition.  A hit with bounces > 0 on a dielectric model, with dir = normalize(r.d) and
+ * ip = r.o + dir * dist as every shade has them; n the normal this shade uses (flat, or
+ * pt_scene_set_model_smooth's); ior the model's; mc the albedo (the model's colour, times its
+ * texture where it has one).  float32 IEEE in exactly this order, no fused multiply-add;
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *   ci  = dot(dir, n)
+ *   ent = ci < 0.0f                              the normal faces the ray: entering
+ *   nn  = ent ? n : -n;   c = ent ? -ci : ci;   c = fminf(c, 1.0f)
+ *   eta = ent ? 1.0f / ior : ior
+ *   k   = 1.0f - (eta*eta) * (1.0f - c*c)
+ *   a   = (1.0f - ior) / (1.0f + ior);   r0 = a*a
+ *   k < 0.0f:   total internal reflection (no draw is made)
+ *   otherwise:  sk = sqrtf(k);   x = 1.0f - (ent ? c : sk);   x2 = x*x;   x5 = (x2*x2)*x
+ *               Fr = r0 + (1.0f - r0) * x5                   (Schlick, cosine on the thin side)
+ *               u  = the first uniform of the engine seeded (iteration, slot, r.bounces)
+ *               u < Fr: reflection, else refraction
+ *   reflection, total internal reflection:
+ *               d' = dir + nn * (2.0f * c);           o' = ip + nn * 0.1f;   colour unchanged
+ *   refraction: d' = dir * eta + nn * (eta*c - sk);   o' = ip - nn * 0.1f;   colour = colour * mc when ent
+ *   then bounces-- as for every surviving material
+ * The mirror direction is the true one; REFLECTIVE, COAT and METAL keep the reference's formula.
+ * The two-sided triangle test lets a ray inside a mesh find the far wall, its t >= -0.005 bound
+ * keeps an origin moved 0.1 past a surface from finding that surface again, and every shade
+ * reseeds its engine, so the one draw disturbs no other stream.  Only the shading computes
+ * anything new: every path that shades a hit (the plain loop, masked and generated iterations,
+ * graph replay, every accel, pipeline count and block size) computes the same bits.  The
+ * sampled first-hit guides and pt_renderer_primary_albedo report mc for a dielectric hit as for
+ * every material.
+ * Limits.  Glass thinner than a few times the 0.1 origin offset is not resolved.  A mesh whose
+ * normals oppose its winding has inside and outside swapped.  A smooth normal near a silhouette
+ * can call an entering ray a leaving one.  The colour tints once per entry, whatever the
+ * thickness: there is no absorption along the path.  There are no nested media and no priority
+ * between overlapping glass models.  Light seen through glass is found by the paths alone, so
+ * caustics are noisy.  Under PT_DENOISE_DEMODULATE a dielectric first hit multiplies by its
+ * albedo only when the sample refracts in: the caveat given there for SPECULAR and REFRACTIVE.
+ * Config grammar: a material block DIELECTRIC / <name> / [r,g,b], like the other material
+ * keywords, and the attribute ior:<number> on MESH, SPHERE and BOX blocks (a malformed value or
+ * one outside [1, 4] is refused: "bad attribute ..."). */
+int pt_scene_set_model_ior(pt_scene *s, int model, float ior);
+float pt_scene_model_ior(const pt_scene *s, int model);
 /* with_bvh: also build the per-mesh BLAS (needed by PT_ACCEL_GRID_FAST and PT_ACCEL_BVH;
  * pt_renderer_allocate_on_gpu adds it on demand to a scene built without it). */
 int pt_scene_build(pt_scene *s, const int grid[3], int with_bvh);
@@ -801,6 +856,14 @@ void pt_renderer_free(pt_renderer *r);
 /* Device math conformance hook: evaluates the kernels' sinf/cosf/powf/sqrtf/div
  * replacements on n inputs (x, y) -> out[n*5] = sin(x) cos(x) pow(x,y) sqrt(x) x/y. */
 int pt_selftest_math(int n, const float *x, const float *y, float *out);
+
+/* Device conformance hook of the dielectric material: evaluates the definition above on n inputs,
+ * one lane each, without a renderer.  dir (n*3) is normalised first, as the shading does; nrm
+ * (n*3) and ior (n) are used as given; u (n) takes the place of the draw.  out_dir (n*3) is d';
+ * out_event (n): 0 refraction entering, 1 refraction leaving, 2 Fresnel reflection, 3 total
+ * internal reflection. */
+int pt_selftest_dielectric(int n, const float *dir, const float *nrm, const float *ior, const float *u,
+                           float *out_dir, int *out_event);
 
 /* main.cpp: load scene config, render cfg->iterations, write BMP. */
 int pt_render(const char *scene_config, const pt_render_config *cfg, const char *bmp_out);

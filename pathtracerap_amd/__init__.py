@@ -51,7 +51,7 @@ _MAX_BOUNCE_COUNTERS = 64
 _DEFERRED_SLOT = 50 + _MAX_BOUNCE_COUNTERS - 1     # kDeferredRayCounter
 # Primitive.h:70-79
 MATERIALS = {"DIFFUSE": 0, "SPECULAR": 1, "REFLECTIVE": 2, "REFRACTIVE": 3,
-             "EMISSIVE": 4, "COAT": 5, "METAL": 6}
+             "EMISSIVE": 4, "COAT": 5, "METAL": 6, "DIELECTRIC": 7}
 
 
 class PathTracerError(RuntimeError):
@@ -116,6 +116,8 @@ EXPORTS = [
     ("pt_scene_add_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
     ("pt_scene_set_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     ("pt_scene_model_smooth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("pt_scene_set_model_ior", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
+    ("pt_scene_model_ior", ctypes.c_float, [ctypes.c_void_p, ctypes.c_int]),
     ("pt_scene_set_mesh_uv", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, ctypes.c_int]),
     ("pt_scene_export_uv", ctypes.c_int, [ctypes.c_void_p, _P_F]),
     ("pt_scene_mesh_has_uv", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -194,6 +196,7 @@ EXPORTS = [
     ("pt_environment_sky", ctypes.c_int, [_P_F, _P_F, _P_F, ctypes.c_int, _P_F]),
     ("pt_renderer_free", None, [ctypes.c_void_p]),
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
+    ("pt_selftest_dielectric", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F, _P_F, _P_F, _P_I]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
 ]
 
@@ -468,7 +471,7 @@ class Scene:
         return _err(lib().pt_scene_add_mesh(self._h, _fp(pos), _fp(nrm), len(pos), _ip(tris), len(tris)), "addMesh")
 
     def addModel(self, mesh: int, scale, rot_deg, translate, material, color, smooth: bool = False,
-                 texture: int | None = None) -> int:
+                 texture: int | None = None, ior: float | None = None) -> int:
         mt = MATERIALS[material] if isinstance(material, str) else int(material)
         s = np.array(scale, np.float32); r = np.array(rot_deg, np.float32)
         t = np.array(translate, np.float32); c = np.array(color, np.float32)
@@ -477,6 +480,8 @@ class Scene:
             self.set_smooth(m)
         if texture is not None:
             self.set_texture(m, texture)
+        if ior is not None:
+            self.set_ior(m, ior)
         return m
 
     def set_mesh_uv(self, mesh: int, uv) -> None:
@@ -534,6 +539,19 @@ class Scene:
         """The smooth flag of every model, a bool array (pt_scene_model_smooth)."""
         n = self.counts()["nmodel"]
         return np.array([_err(lib().pt_scene_model_smooth(self._h, i), "smooth") != 0 for i in range(n)], bool)
+
+    def set_ior(self, model: int | None = None, ior: float = 1.5) -> None:
+        """The index of refraction of ``model`` (None: every model added so far), finite and in
+        [1, 4] (pt_scene_set_model_ior).  Stored for every model, read only by a DIELECTRIC one.
+        Before or after ``build``; a renderer reads the values in ``allocateOnGPU``."""
+        _err(lib().pt_scene_set_model_ior(self._h, -1 if model is None else int(model), float(ior)), "set_ior")
+
+    def ior(self, model: int) -> float:
+        """The index of refraction of ``model``, 1.5 unless set (pt_scene_model_ior)."""
+        v = lib().pt_scene_model_ior(self._h, int(model))
+        if v < 0:
+            _err(-1, "ior")
+        return float(v)
 
     def build(self, grid=(25, 25, 25), bvh: bool = True) -> None:
         """addMeshesToGrid (grid) + the per-mesh BLAS that ACCEL_GRID_FAST / ACCEL_BVH
@@ -606,6 +624,24 @@ def selftest_math(x, y) -> np.ndarray:
     out = np.zeros((len(x), 5), np.float32)
     _err(lib().pt_selftest_math(len(x), _fp(x), _fp(y), _fp(out)), "selftest_math")
     return out
+
+
+def selftest_dielectric(dirs, normals, ior, u):
+    """Device evaluation of the dielectric material's definition (pt_selftest_dielectric):
+    ``dirs`` (n, 3) are normalised first, ``normals`` (n, 3) and ``ior`` (n) used as given, ``u``
+    (n) takes the place of the draw.  Returns (directions (n, 3), events (n): 0 refraction
+    entering, 1 refraction leaving, 2 Fresnel reflection, 3 total internal reflection)."""
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    n = len(d)
+    io = np.ascontiguousarray(np.broadcast_to(np.asarray(ior, np.float32), (n,)))
+    uu = np.ascontiguousarray(np.broadcast_to(np.asarray(u, np.float32), (n,)))
+    if len(nr) != n:
+        raise PathTracerError("selftest_dielectric: dirs and normals differ in length")
+    out = np.zeros((n, 3), np.float32)
+    ev = np.zeros(n, np.int32)
+    _err(lib().pt_selftest_dielectric(n, _fp(d), _fp(nr), _fp(io), _fp(uu), _fp(out), _ip(ev)), "selftest_dielectric")
+    return out, ev
 
 
 class Renderer:

@@ -129,6 +129,15 @@ int pt_scene_model_smooth(const pt_scene* s, int model) {
     return rc < 0 ? set_err("pt_scene_model_smooth: bad model index") : rc;
 }
 
+int pt_scene_set_model_ior(pt_scene* s, int model, float ior) { SCENE_CALL(s->s.setModelIor(model, ior)); }
+
+float pt_scene_model_ior(const pt_scene* s, int model) {
+    if (!s) { set_err("null scene"); return -1.0f; }
+    const float v = s->s.modelIor(model);
+    if (v < 0.0f) set_err("pt_scene_model_ior: bad model index");
+    return v;
+}
+
 int pt_scene_set_mesh_uv(pt_scene* s, int mesh, const float* uv, int nv) {
     if (!uv) return set_err("pt_scene_set_mesh_uv: null argument");
     SCENE_CALL(s->s.setMeshUv(mesh, uv, nv));
@@ -574,6 +583,14 @@ int pt_selftest_math(int n, const float* x, const float* y, float* out) {
     if (n < 0 || (n > 0 && (!x || !y || !out))) return set_err("bad arguments");
     std::string e;
     if (pt::selftest_math(n, x, y, out, &e) < 0) return set_err(e);
+    return 0;
+}
+
+int pt_selftest_dielectric(int n, const float* dir, const float* nrm, const float* ior, const float* u, float* out_dir,
+                           int* out_event) {
+    if (n < 0 || (n > 0 && (!dir || !nrm || !ior || !u || !out_dir || !out_event))) return set_err("bad arguments");
+    std::string e;
+    if (pt::selftest_dielectric(n, dir, nrm, ior, u, out_dir, out_event, &e) < 0) return set_err(e);
     return 0;
 }
 

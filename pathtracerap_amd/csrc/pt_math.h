@@ -24,7 +24,8 @@ constexpr float kSqrtOneThird = 0.5773502691896257645091487805019574556476f;
 // Primitive.h:70-79 Material::MaterialType
 enum MaterialType : int {
     MAT_DIFFUSE = 0, MAT_SPECULAR = 1, MAT_REFLECTIVE = 2, MAT_REFRACTIVE = 3,
-    MAT_EMISSIVE = 4, MAT_COAT = 5, MAT_METAL = 6
+    MAT_EMISSIVE = 4, MAT_COAT = 5, MAT_METAL = 6,
+    MAT_DIELECTRIC = 7      // glass (no counterpart in the reference): scatter_dielectric
 };
 
 struct f3 { float x, y, z; };
@@ -259,6 +260,40 @@ PT_HD f3 scatter_coat(f3 n, f3 d, Rng& rng) {
     float roulette = rng.u01();
     if (roulette < 0.5f) return reflect_ref(d, n);
     return scatter_hemisphere(n, rng);
+}
+
+// The dielectric (glass) event of a hit (no counterpart in the reference;
+// include/pathtracer_amd.h, "Dielectric material", states it operation by operation).
+// dir: the normalised ray direction; n: the shading normal; u: the shade's first uniform (not
+// read under total internal reflection).  nn: the normal on the ray's side; the caller moves
+// the origin 0.1 along it (a reflection) or against it (a refraction) and multiplies the colour
+// by the albedo on DIEL_REFRACT_IN alone.
+enum DielectricEvent : int { DIEL_REFRACT_IN = 0, DIEL_REFRACT_OUT = 1, DIEL_REFLECT = 2, DIEL_TIR = 3 };
+struct Dielectric { f3 d, nn; int event; };
+PT_HD Dielectric scatter_dielectric(f3 dir, f3 n, float ior, float u) {
+    Dielectric q;
+    const float ci = dot(dir, n);
+    const bool ent = ci < 0.0f;
+    q.nn = ent ? n : mk3(-n.x, -n.y, -n.z);
+    float c = ent ? -ci : ci;
+    c = fminf(c, 1.0f);
+    const float eta = ent ? 1.0f / ior : ior;
+    const float k = 1.0f - (eta * eta) * (1.0f - c * c);
+    const float a = (1.0f - ior) / (1.0f + ior);
+    const float r0 = a * a;
+    q.event = DIEL_TIR;
+    float sk = 0.0f;
+    if (!(k < 0.0f)) {
+        sk = sqrtf(k);
+        const float x = 1.0f - (ent ? c : sk);
+        const float x2 = x * x;
+        const float x5 = (x2 * x2) * x;
+        const float fr = r0 + (1.0f - r0) * x5;
+        q.event = u < fr ? DIEL_REFLECT : (ent ? DIEL_REFRACT_IN : DIEL_REFRACT_OUT);
+    }
+    if (q.event >= DIEL_REFLECT) q.d = dir + q.nn * (2.0f * c);
+    else q.d = dir * eta + q.nn * (eta * c - sk);
+    return q;
 }
 
 // calculateMetalScattering (utility.h:145-170)

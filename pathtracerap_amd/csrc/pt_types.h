@@ -61,7 +61,9 @@ struct ModelShade {
     int smooth;           // 1: the hit normal interpolates the vertex normals (pt_scene_set_model_smooth)
     int texture;          // the albedo texture's index (pt_scene_set_model_texture), -1: none; read only
                           // when the renderer holds textures (KParams::tex)
-    int pad[2];
+    float ior;            // the index of refraction (pt_scene_set_model_ior); read only for a hit on a
+                          // MAT_DIELECTRIC model
+    int pad;
 };
 static_assert(sizeof(ModelShade) == 32, "ModelShade layout");
 

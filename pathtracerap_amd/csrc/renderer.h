@@ -134,6 +134,9 @@ struct KParams {
                                         // Static per allocation.  Last, for the same reason
     float4* cache_albedo;               // with tex: the albedo of each pixel's cached primary hit (k_primary),
                                         // which bounce 0 multiplies by instead of ModelShade::color; else null
+    const ModelShade* glass;            // `shade` again in a scene with a MAT_DIELECTRIC model, else null: it picks
+                                        // the hit-buffer pass's GLASS forms at launch.  Static per allocation.  Last,
+                                        // for the same reason
 };
 
 // denoise(): the largest a-trous step whose pass stages its tile in LDS (PT_DENOISE_LDS overrides)
@@ -355,5 +358,8 @@ private:
 
 // Device math conformance hook (pt_selftest_math).
 int selftest_math(int n, const float* x, const float* y, float* out, std::string* err);
+// Device conformance hook of the dielectric material (pt_selftest_dielectric).
+int selftest_dielectric(int n, const float* dir, const float* nrm, const float* ior, const float* u, float* out_dir,
+                        int* out_event, std::string* err);
 
 }  // namespace pt

@@ -1312,7 +1312,11 @@ struct RayState { f3 o, d, c; int pixel, bounces; };
 // mt, mc: the hit model's material type and colour, read only for a hit of a ray with
 // bounces left (shade() loads them then; the hit-buffer pass has them loaded already).
 // env: KParams::env (a kernel argument: wave-uniform); its record is read only by a ray that misses.
-__device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, int slot, int mt, f3 mc, const EnvRec* env) {
+// ior: the model's, read only for a MAT_DIELECTRIC hit.  GLASS = false: a kernel never launched
+// for a scene with a dielectric model, which compiles none of that branch.
+template <bool GLASS = true>
+__device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, int slot, int mt, f3 mc, const EnvRec* env,
+                                          float ior = 1.5f) {
     if (r.bounces <= 0) r.c = r.c * mk3(0.01f, 0.01f, 0.01f);
     if (h.dist < kFMax) {
         const f3 dir = normalize(r.d);
@@ -1334,6 +1338,14 @@ __device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, i
                 const f3 rr = reflect_ref(dir, h.n);
                 r.o = ip + h.n * 0.1f;
                 r.d = rr;
+            } else if (GLASS && mt == MAT_DIELECTRIC) {
+                // the dielectric material (include/pathtracer_amd.h, "Dielectric material")
+                Rng rng = Rng::make(iter, slot, r.bounces);
+                const Dielectric q = scatter_dielectric(dir, h.n, ior, rng.u01());
+                const f3 off = q.nn * 0.1f;
+                r.o = q.event >= DIEL_REFLECT ? ip + off : ip - off;
+                r.d = q.d;
+                if (q.event == DIEL_REFRACT_IN) r.c = r.c * mc;
             }
         }
     } else {
@@ -1349,13 +1361,16 @@ __device__ __forceinline__ void shade_mat(RayState& r, const Hit& h, int iter, i
 // left in p.cache_albedo.  Without textures the albedo is the model's colour, as it was.
 // MAYTEX = false: a kernel never launched for a textured scene, which compiles none of it.
 constexpr int kTriCached = -2;
-template <bool MAYTEX = true>
+// MAYGLASS = false: a kernel never launched for a scene with a dielectric model, likewise.
+template <bool MAYTEX = true, bool MAYGLASS = true>
 __device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& h, int iter, int slot, int tri) {
     int mt = 0;
     f3 mc = mk3(0, 0, 0);
+    float ior = 1.5f;
     if (h.dist < kFMax && r.bounces > 0) {
         const ModelShade& S = p.shade[h.model];
         mt = S.mat_type;
+        if (MAYGLASS) ior = S.ior;                  // the same record: the round trip of mat_type
         mc = mk3(S.color[0], S.color[1], S.color[2]);
         if (MAYTEX && p.tex) {
             if (tri == kTriCached) {
@@ -1366,7 +1381,7 @@ __device__ __forceinline__ void shade(const KParams& p, RayState& r, const Hit& 
             }
         }
     }
-    shade_mat(r, h, iter, slot, mt, mc, p.env);
+    shade_mat<MAYGLASS>(r, h, iter, slot, mt, mc, p.env, ior);
 }
 
 // ---------------------------------------------------------------------------
@@ -2746,7 +2761,10 @@ __global__ __launch_bounds__(BS) void k_trace_deferred(KParams p, int bounce) {
 // instantiation picked at launch, so the pass of every other scene keeps the registers it
 // had (42 VGPRs against 64); the other forms test the pointer where they compute a normal.
 // TEX (with SMOOTH): the pass of a scene with a textured model (KParams::tex set), likewise.
-template <bool FIRST, int ACCEL, int BS, bool SMOOTH = false, bool TEX = false>
+// GLASS: the pass of a scene with a dielectric model (KParams::glass set), likewise: it loads the
+// model's ior with its material type and compiles shade_mat's dielectric branch.  The other
+// forms (bounce 0, the fused bounce, ACCEL_GRID) test the material at run time.
+template <bool FIRST, int ACCEL, int BS, bool SMOOTH = false, bool TEX = false, bool GLASS = false>
 __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_MINWAVES) void k_bounce(KParams p, int iter, int bounce) {
     __shared__ int s_stack[(!FIRST && ACCEL != ACCEL_GRID && ACCEL != kAccelHitBuffer) ? kStack * BS : 1];
     __shared__ int4 s_hs[(!FIRST && ACCEL == ACCEL_GRID_FAST) ? kHitCap * BS : 1];
@@ -2786,6 +2804,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             for (int q = 0; q < 9; q++) nm[q] = p.models[mi].nm[q];
             const ModelShade& S = p.shade[mi];
             const int mt = S.mat_type;
+            const float ior = GLASS ? S.ior : 1.5f;
             f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
             const float4 tn = tri >= 0 ? tnl : make_float4(0, 0, 0, 0);
             f3 hn = normalize(xform_normal9(nm, mk3(tn.x, tn.y, tn.z)));
@@ -2816,7 +2835,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
             h.dist = hh.x;
             h.model = hm;
             h.n = hm >= 0 ? hn : mk3(0, 0, 0);
-            shade_mat(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc, p.env);
+            shade_mat<GLASS>(r, h, iter >= 0 ? iter : *p.iter_dev, j, mt, mc, p.env, ior);
         }
     } else if (active) {
         int tri = kTriCached;
@@ -2837,7 +2856,7 @@ __global__ __launch_bounds__(BS, (ACCEL == ACCEL_GRID_FAST && !FIRST) ? 3 : PT_M
                 h = intersect_scene<ACCEL, BS>(p, r.o, r.d, s_stack + threadIdx.x, s_hs + threadIdx.x, tri);
             }
         }
-        shade<TEX || FIRST || ACCEL != kAccelHitBuffer>(p, r, h, iter >= 0 ? iter : *p.iter_dev, j, tri);   // -1: hipGraph replay reads the id
+        shade<TEX || FIRST || ACCEL != kAccelHitBuffer, GLASS || FIRST || ACCEL != kAccelHitBuffer>(p, r, h, iter >= 0 ? iter : *p.iter_dev, j, tri);   // -1: hipGraph replay reads the id
     }
     const bool alive = active && r.bounces > 0;
     if (active && !alive) {
@@ -3314,6 +3333,17 @@ __global__ __launch_bounds__(256) void k_guide_first(KParams p, float* __restric
     dst[1] = b;
 }
 
+// Test hook (pt_selftest_dielectric): scatter_dielectric for caller-given inputs, one lane each.
+__global__ __launch_bounds__(256) void k_selftest_dielectric(int n, const float* dir, const float* nrm, const float* ior,
+                                                             const float* u, float* out_dir, int* out_event) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const f3 d = normalize(mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+    const Dielectric q = scatter_dielectric(d, mk3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), ior[i], u[i]);
+    out_dir[3 * i] = q.d.x; out_dir[3 * i + 1] = q.d.y; out_dir[3 * i + 2] = q.d.z;
+    out_event[i] = q.event;
+}
+
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
@@ -3480,13 +3510,17 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     tex_bytes = 0;
     alloc_ntris = (int)scene.triangles.size();
     alloc_color.resize(scene.model_shade.size() * 3);
-    bool any_smooth = false, any_tex = false;
+    bool any_smooth = false, any_tex = false, any_glass = false;
     for (size_t i = 0; i < scene.model_shade.size(); i++) {
         const ModelShade& sh = scene.model_shade[i];
         any_smooth |= sh.smooth != 0;
         any_tex |= sh.texture >= 0;
+        any_glass |= sh.mat_type == MAT_DIELECTRIC;
         for (int k = 0; k < 3; k++) alloc_color[3 * i + k] = sh.color[k];
     }
+    // the dielectric material: the iors as they are now (likewise); the pointer only picks the
+    // shading pass's GLASS forms at launch
+    kp.glass = any_glass ? kp.shade : nullptr;
     if (any_smooth || any_tex) {
         std::vector<TriShade> tab(std::max<size_t>(scene.triangles.size(), 1), TriShade{});   // record 0 always exists
         for (size_t t = 0; t < scene.triangles.size(); t++) {
@@ -3819,7 +3853,13 @@ void Renderer::launchTrace(const KParams& k, hipStream_t st, int b) {
 
 template <bool FIRST, int BS>
 static void launch_bounce_bs(int accel, dim3 grid, hipStream_t st, const KParams& kp, int iter, int b) {
-    if (accel == kAccelHitBuffer && kp.tex && !FIRST)
+    if (accel == kAccelHitBuffer && kp.glass && !FIRST) {
+        // a scene with a dielectric model: the pass's GLASS forms
+        if (kp.tex) hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true, true, true>), grid, dim3(BS), 0, st, kp, iter, b);
+        else if (kp.smooth)
+            hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true, false, true>), grid, dim3(BS), 0, st, kp, iter, b);
+        else hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, false, false, true>), grid, dim3(BS), 0, st, kp, iter, b);
+    } else if (accel == kAccelHitBuffer && kp.tex && !FIRST)
         hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true, true>), grid, dim3(BS), 0, st, kp, iter, b);
     else if (accel == kAccelHitBuffer && kp.smooth && !FIRST)
         hipLaunchKernelGGL((k_bounce<false, kAccelHitBuffer, BS, true>), grid, dim3(BS), 0, st, kp, iter, b);
@@ -4538,6 +4578,33 @@ int selftest_math(int n, const float* x, const float* y, float* out, std::string
     if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 20, hipMemcpyDeviceToHost);
     hipFree(dx); hipFree(dy); hipFree(dout);
     if (e != hipSuccess) { *err = std::string("selftest_math: ") + hipGetErrorString(e); return -1; }
+    return 0;
+}
+
+int selftest_dielectric(int n, const float* dir, const float* nrm, const float* ior, const float* u, float* out_dir,
+                        int* out_event, std::string* err) {
+    if (n == 0) return 0;
+    const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4;
+    float *dd = nullptr, *dn = nullptr, *di = nullptr, *du = nullptr, *dout = nullptr;
+    int* dev = nullptr;
+    hipError_t e = hipMalloc(&dd, n3);
+    if (e == hipSuccess) e = hipMalloc(&dn, n3);
+    if (e == hipSuccess) e = hipMalloc(&di, n1);
+    if (e == hipSuccess) e = hipMalloc(&du, n1);
+    if (e == hipSuccess) e = hipMalloc(&dout, n3);
+    if (e == hipSuccess) e = hipMalloc(&dev, n1);
+    if (e == hipSuccess) e = hipMemcpy(dd, dir, n3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dn, nrm, n3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(di, ior, n1, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(du, u, n1, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_selftest_dielectric, dim3((n + 255) / 256), dim3(256), 0, 0, n, dd, dn, di, du, dout, dev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_dir, dout, n3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_event, dev, n1, hipMemcpyDeviceToHost);
+    hipFree(dd); hipFree(dn); hipFree(di); hipFree(du); hipFree(dout); hipFree(dev);
+    if (e != hipSuccess) { *err = std::string("selftest_dielectric: ") + hipGetErrorString(e); return -1; }
     return 0;
 }
 

@@ -299,7 +299,7 @@ int Scene::addMesh(const float* p, const float* n, int nv, const int* tris, int 
 int Scene::addModel(int mesh_index, const float scale[3], const float rot_deg[3], const float translate[3],
                     int material_type, const float color[3]) {
     if (mesh_index < 0 || mesh_index >= (int)meshes.size()) { last_error = "addModel: bad mesh index"; return -1; }
-    if (material_type < MAT_DIFFUSE || material_type > MAT_METAL) { last_error = "addModel: bad material"; return -1; }
+    if (material_type < MAT_DIFFUSE || material_type > MAT_DIELECTRIC) { last_error = "addModel: bad material"; return -1; }
     Model m;
     m.mesh_index = mesh_index;
     model_matrices(scale, rot_deg, translate, m.model_to_world, m.world_to_model);
@@ -322,6 +322,21 @@ int Scene::setModelSmooth(int model, bool on) {
 int Scene::modelSmooth(int model) const {
     if (model < 0 || model >= (int)models.size()) return -1;
     return models[model].smooth ? 1 : 0;
+}
+
+int Scene::setModelIor(int model, float ior) {
+    if (model < -1 || model >= (int)models.size()) { last_error = "setModelIor: bad model index"; return -1; }
+    if (!std::isfinite(ior) || ior < 1.0f || ior > 4.0f) { last_error = "setModelIor: ior must be finite and in [1, 4]"; return -1; }
+    for (int i = model < 0 ? 0 : model; i < (model < 0 ? (int)models.size() : model + 1); i++) {
+        models[i].ior = ior;
+        if (model_shade.size() == models.size()) model_shade[i].ior = ior;   // built: the value alone changes
+    }
+    return 0;
+}
+
+float Scene::modelIor(int model) const {
+    if (model < 0 || model >= (int)models.size()) return -1.0f;
+    return models[model].ior;
 }
 
 int Scene::setMeshUv(int mesh, const float* uv, int nv) {
@@ -452,6 +467,7 @@ static int material_from_name(const std::string& k) {
     if (k == "EMISSIVE") return MAT_EMISSIVE;
     if (k == "COAT") return MAT_COAT;
     if (k == "METAL") return MAT_METAL;
+    if (k == "DIELECTRIC") return MAT_DIELECTRIC;
     return -1;
 }
 
@@ -645,6 +661,7 @@ int Scene::loadConfig(const std::string& path) {
         Mat mat; mat.type = MAT_DIFFUSE; mat.color[0] = mat.color[1] = mat.color[2] = 0.98f;
         bool smooth = false;
         int texture = -1;
+        float ior = 1.5f;
         for (size_t i = first_attr; i < b.size(); i++) {
             std::string key = b[i].substr(0, b[i].find(':'));
             std::string val = b[i].find(':') == std::string::npos ? "" : trim(b[i].substr(b[i].find(':') + 1));
@@ -666,6 +683,14 @@ int Scene::loadConfig(const std::string& path) {
                 smooth = val == "smooth";
                 continue;
             }
+            if (key == "ior") {
+                char* end = nullptr;
+                const double num = std::strtod(val.c_str(), &end);
+                if (val.empty() || !end || *end != 0 || !std::isfinite(num) || num < 1.0 || num > 4.0)
+                    return fail("bad attribute " + b[i]);
+                ior = (float)num;
+                continue;
+            }
             if (!parse_vec(val, v) || v.size() != 3) return fail("bad attribute " + b[i]);
             float f[3] = {(float)v[0], (float)v[1], (float)v[2]};
             if (key == "translate") std::memcpy(tr, f, sizeof f);
@@ -676,6 +701,7 @@ int Scene::loadConfig(const std::string& path) {
         const int model = addModel(mesh, scale, rot, tr, mat.type, mat.color);
         if (model < 0) return -4;
         models[model].smooth = smooth;
+        models[model].ior = ior;
         if (texture >= 0 && setModelTexture(model, texture) < 0) return fail(last_error);
     }
     if (models.empty()) return fail("scene has no MESH/BOX/SPHERE instances");
@@ -799,6 +825,7 @@ void Scene::buildDeviceTables() {
         sh.mat_type = m.mat.material_type;
         sh.smooth = m.smooth ? 1 : 0;
         sh.texture = m.texture;
+        sh.ior = m.ior;
         world_box(m, mesh, r.bvh_root, r.wbox);
         // Bounded hit-set collection (ACCEL_GRID_FAST).  A member h whose voxel box the
         // DDA enters at ray parameter tau has its hit within tau + R_h, R_h = the diameter

@@ -39,6 +39,7 @@ struct Model {                                          // Primitive.h:94-101
     Material mat;
     bool smooth = false;                                // setModelSmooth: shade with interpolated vertex normals
     int texture = -1;                                   // setModelTexture: index into Scene::textures, -1: none
+    float ior = 1.5f;                                   // setModelIor: read only by a MAT_DIELECTRIC model's shade
 };
 struct Texture { int w = 0, h = 0; std::vector<float> rgb; };   // w*h texels, texel (y, x) at 3*(y*w + x); linear values
 struct Voxel { IndexRange entity_index_range; int entity_type = ENTITY_TRIANGLE; };  // Primitive.h:123-127
@@ -78,6 +79,11 @@ public:
     // so far.  Any time after the model exists; the grid and the BLAS are not touched.
     int setModelSmooth(int model, bool on);
     int modelSmooth(int model) const;                   // 0 / 1, negative: bad index
+    // Per-model index of refraction of the dielectric material (no counterpart in the reference):
+    // finite and in [1, 4], 1.5 by default; model -1 = every model added so far.  Stored for every
+    // model, read only by a MAT_DIELECTRIC one.  Before or after build, like the smooth flag.
+    int setModelIor(int model, float ior);
+    float modelIor(int model) const;                    // negative: bad index
     // Albedo textures (no counterpart in the reference, whose Primitive.h declares a uv and never
     // reads it).  Per-vertex uv of one mesh, in addMesh's vertex order; the grid and the BLAS are
     // not touched.  A texture is w x h RGB texels; a model binds one (-1: none; model -1: every
