@@ -865,6 +865,77 @@ int pt_selftest_math(int n, const float *x, const float *y, float *out);
 int pt_selftest_dielectric(int n, const float *dir, const float *nrm, const float *ior, const float *u,
                            float *out_dir, int *out_event);
 
+/* ---- Direct lighting: light sampling with shadow rays at diffuse hits (added; no counterpart in
+ * the reference, whose paths carry light only when the random walk lands on an EMISSIVE triangle).
+ * Opt-in: a renderer that never calls pt_renderer_set_direct_light allocates, launches and
+ * computes exactly what it did, and so does one with the switch on in a scene without a light.
+ *
+ * Lights are the triangles of every EMISSIVE model, models in index order, each model's triangles
+ * in mesh order.  The table holds per light, in world space: p0, e1, e2 (the first vertex and the
+ * two edges), the unit normal nl, the area, the model index and the emission E (the model's
+ * colour; two-sided, as the shade has no facing test); and A_total and a float32 cdf (the running
+ * area sum over A_total, last entry 1).  Computed in double from the float32 vertices and
+ * model_to_world, rounded once.  A zero-area triangle stays in the table and is never chosen.
+ *
+ * The estimator, float32, no contraction, in this order.  At every hit of a live ray (bounces > 0,
+ * the count before the shade decrements it) on a MAT_DIFFUSE model -- COAT, METAL, REFLECTIVE and
+ * DIELECTRIC hits sample nothing -- with ip the hit point, n the shading normal, mc the albedo and
+ * c the ray's colour, all as the shade of that hit has them, and slot the slot that shade seeds
+ * with (the pixel index at a cached primary hit, the dense slot otherwise):
+ *   u0, u1, u2 = the first uniform of the engine seeded (iteration, slot, 256 + bounces),
+ *                (iteration, slot, 320 + bounces), (iteration, slot, 384 + bounces)
+ *   i  = the smallest index with u0 < cdf[i], else the last light
+ *   s  = sqrtf(u1);  y = (p0 + e1 * (s * (1 - u2))) + e2 * (s * u2)
+ *   x' = ip + n * 0.1f                               (the origin a scattered ray gets)
+ *   w  = y - x';  r2 = dot(w, w);  r = sqrtf(r2);  wn = w * (1 / sqrtf(dot(w, w)))
+ *   cx = dot(n, wn);  cy = fabsf(dot(nl, wn))
+ *   unless (cx > 0 && cy > 0 && r2 > 0): nothing is added, no shadow ray is traced (a NaN fails)
+ *   g  = ((cx * cy) / (pi * r2)) * A_total;  Dc = ((c * mc) * E) * g      per channel
+ *   the shadow ray runs from x' along wn with tmax = r * 0.999f; it is occluded if and only if
+ *   some triangle of some model that the reference's triangle test accepts lies at a world
+ *   distance (the closest-hit query's distance of that triangle) below tmax -- PT_ACCEL_BVH's
+ *   exact semantics for every accel; the grid's early exit never applies to a shadow ray
+ *   unoccluded: D[pixel] += Dc
+ * A ray that hits an EMISSIVE model directly after a DIFFUSE vertex contributes nothing for that
+ * hit (the vertex before it sampled the lights); emission reached from the camera or through
+ * COAT, METAL, REFLECTIVE or DIELECTRIC counts as it did.  Per pixel and iteration, with t the
+ * value the path's end writes (sqrtf of the terminal colour) and t' = 0 where that terminal was
+ * such a suppressed hit, else t:  sample = (D == 0) ? t' : sqrtf(t' * t' + D)  per channel, which
+ * goes into the image and its square into the moments.  A pixel that received no direct light
+ * keeps the bits it had.
+ * Limits: no multiple importance sampling, so the 1 / r2 term is unbounded close to a light (a
+ * diffuse surface next to a lamp shows bright outliers); the environment map is not sampled;
+ * COAT and METAL hits do not sample; emission textures are refused.
+ *
+ * pt_renderer_set_direct_light: before or after allocate_on_gpu; after it, a change clears the
+ * accumulators as pt_renderer_set_environment does and drops captured graphs.  Refused with a
+ * message, before any launch (here when the renderer is allocated, else at allocate_on_gpu):
+ * PT_ACCEL_GRID or a fused trace (PT_TRACE_SPLIT=0 / PT_GF_SPLIT=0); moments not enabled; an
+ * EMISSIVE model with a texture; max_bounces > 63 (the depth codes above would meet the shade's
+ * and the jitter's).
+ * pt_renderer_direct_light: the switch, and the allocation's light count and A_total (0 before).
+ * pt_scene_lights / pt_renderer_lights: the table of a scene / of the renderer's allocation, up to
+ * max_lights records of PT_LIGHT_FLOATS floats: p0[3], area, e1[3], model (an int's bits), e2[3],
+ * cdf, nl[3], 0, E[3], 0; *area_total = A_total; returns the number of lights.
+ * pt_scene_direct_light: 1 when the scene file's RENDER block says direct_light: 1.
+ * pt_renderer_occluded (test hook): n segments orig -> target (n*3 floats each) as shadow rays,
+ * direction the normalised difference and tmax = 0.999f * |target - orig|; out[i] = 1 occluded,
+ * 0 not; a segment of zero length reads 0.  Needs a BLAS (not PT_ACCEL_GRID).
+ * pt_renderer_direct_sample (test hook): the estimator for n caller-given hits: rays (orig, dir),
+ * distance, model, scene triangle, colour c, and ids (iteration, slot, bounces) per hit; the
+ * normal and the albedo are the shade's for such a hit.  out_f: 8 floats per hit (y[3], g, Dc[3],
+ * 0); out_i: the light's index (-1: the geometry test failed, the rest is 0) and 1 if unoccluded. */
+#define PT_LIGHT_FLOATS 20
+int pt_renderer_set_direct_light(pt_renderer *r, int on);
+int pt_renderer_direct_light(pt_renderer *r, int *on, int *n_lights, float *area);
+int pt_scene_lights(const pt_scene *s, int max_lights, float *recs_out, float *area_total);
+int pt_renderer_lights(pt_renderer *r, int max_lights, float *recs_out, float *area_total);
+int pt_scene_direct_light(const pt_scene *s);
+int pt_renderer_occluded(pt_renderer *r, int n, const float *orig, const float *target, int *out);
+int pt_renderer_direct_sample(pt_renderer *r, int n, const float *orig, const float *dir, const float *dist,
+                              const int *model, const int *tri, const float *color, const int *ids, float *out_f,
+                              int *out_i);
+
 /* main.cpp: load scene config, render cfg->iterations, write BMP. */
 int pt_render(const char *scene_config, const pt_render_config *cfg, const char *bmp_out);
 

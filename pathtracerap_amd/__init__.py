@@ -198,7 +198,29 @@ EXPORTS = [
     ("pt_selftest_math", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F]),
     ("pt_selftest_dielectric", ctypes.c_int, [ctypes.c_int, _P_F, _P_F, _P_F, _P_F, _P_F, _P_I]),
     ("pt_render", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_Cfg), ctypes.c_char_p]),
+    ("pt_renderer_set_direct_light", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("pt_renderer_direct_light", ctypes.c_int, [ctypes.c_void_p, _P_I, _P_I, _P_F]),
+    ("pt_scene_lights", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F]),
+    ("pt_renderer_lights", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F]),
+    ("pt_scene_direct_light", ctypes.c_int, [ctypes.c_void_p]),
+    ("pt_renderer_occluded", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_I]),
+    ("pt_renderer_direct_sample", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P_F, _P_F, _P_F, _P_I, _P_I, _P_F, _P_I,
+                                                 _P_F, _P_I]),
 ]
+LIGHT_FLOATS = 20
+
+
+def _light_table(call, what) -> dict:
+    """The light table behind ``call(max_lights, recs, area)`` (pt_scene_lights / pt_renderer_lights)
+    -> dict(p0, e1, e2, nl, emission (n, 3), area, cdf (n,) float32, model (n,) int32, area_total)."""
+    area = ctypes.c_float()
+    n = _err(call(0, None, ctypes.byref(area)), what)
+    recs = np.zeros((n, LIGHT_FLOATS), np.float32)
+    if n:
+        _err(call(n, _fp(recs), ctypes.byref(area)), what)
+    return dict(p0=recs[:, 0:3].copy(), area=recs[:, 3].copy(), e1=recs[:, 4:7].copy(),
+                model=recs[:, 7].copy().view(np.int32), e2=recs[:, 8:11].copy(), cdf=recs[:, 11].copy(),
+                nl=recs[:, 12:15].copy(), emission=recs[:, 16:19].copy(), area_total=np.float32(area.value))
 
 
 def lib() -> ctypes.CDLL:
@@ -460,6 +482,15 @@ class Scene:
         out = _Camera()
         rc = _err(lib().pt_scene_camera(self._h, int(width), int(height), ctypes.byref(out)), "scene camera")
         return Camera.from_c(out) if rc > 0 else None
+
+    def direct_light(self) -> bool:
+        """Whether the config's RENDER block asked for direct lighting (direct_light: 1)."""
+        return bool(_err(lib().pt_scene_direct_light(self._h), "scene direct_light"))
+
+    def lights(self) -> dict:
+        """The light table of direct lighting for the scene as it stands (pt_scene_lights): the
+        world-space triangles of every EMISSIVE model; see ``Renderer.lights``."""
+        return _light_table(lambda n, recs, area: lib().pt_scene_lights(self._h, n, recs, area), "scene lights")
 
     def loadAndProcessMeshFile(self, path: str) -> int:
         return _err(lib().pt_scene_load_obj(self._h, os.fsencode(path)), f"load {path}")
@@ -1006,6 +1037,54 @@ class Renderer:
         out = np.empty_like(d)
         _err(lib().pt_renderer_env_lookup(self._h, len(d), _fp(d), _fp(out)), "env_lookup")
         return out
+
+    def set_direct_light(self, on: bool = True) -> None:
+        """Direct lighting (include/pathtracer_amd.h, "Direct lighting"): while on, every diffuse
+        hit samples one point of one EMISSIVE triangle through a shadow ray.  Needs moments, the
+        split trace (not ACCEL_GRID) and max_bounces <= 63.  Before or after allocateOnGPU; a
+        change after it starts a new render."""
+        _err(lib().pt_renderer_set_direct_light(self._h, 1 if on else 0), "set_direct_light")
+
+    def direct_light(self):
+        """-> (on, lights, area): the switch, and the allocation's light count and total area."""
+        on, n, area = ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+        _err(lib().pt_renderer_direct_light(self._h, ctypes.byref(on), ctypes.byref(n), ctypes.byref(area)), "direct_light")
+        return bool(on.value), int(n.value), float(area.value)
+
+    def lights(self) -> dict:
+        """The allocation's light table (pt_renderer_lights): dict(p0, e1, e2, nl, emission (n, 3),
+        area, cdf (n,), model (n,), area_total); empty before allocateOnGPU."""
+        return _light_table(lambda n, recs, area: lib().pt_renderer_lights(self._h, n, recs, area), "lights")
+
+    def occluded(self, orig, target) -> np.ndarray:
+        """Test hook: the shadow-ray decision for the (n, 3) segments ``orig`` -> ``target``
+        (pt_renderer_occluded) -> (n,) bool; a segment of zero length reads False."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(target, np.float32).reshape(-1, 3)
+        if len(o) != len(t):
+            raise PathTracerError("occluded: arrays differ in length")
+        out = np.zeros(len(o), np.int32)
+        _err(lib().pt_renderer_occluded(self._h, len(o), _fp(o), _fp(t), _ip(out)), "occluded")
+        return out != 0
+
+    def direct_sample(self, orig, dirs, dist, model, tri, color, it, slot, bounces) -> dict:
+        """Test hook: the light sample of caller-given hits (pt_renderer_direct_sample) ->
+        dict(light (n,) int32, -1 where the geometry test failed; y (n, 3); g (n,); dc (n, 3);
+        visible (n,) bool)."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        n = len(o)
+        dd = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(dist, np.float32).reshape(-1)
+        m = np.ascontiguousarray(model, np.int32).reshape(-1)
+        tr = np.ascontiguousarray(tri, np.int32).reshape(-1)
+        c = np.ascontiguousarray(color, np.float32).reshape(-1, 3)
+        ids = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(a, np.int32), (n,)) for a in (it, slot, bounces)], 1))
+        if not (len(dd) == len(t) == len(m) == len(tr) == len(c) == n):
+            raise PathTracerError("direct_sample: arrays differ in length")
+        of, oi = np.zeros((n, 8), np.float32), np.zeros((n, 2), np.int32)
+        _err(lib().pt_renderer_direct_sample(self._h, n, _fp(o), _fp(dd), _fp(t), _ip(m), _ip(tr), _fp(c), _ip(ids), _fp(of),
+                                             _ip(oi)), "direct_sample")
+        return dict(light=oi[:, 0].copy(), y=of[:, 0:3].copy(), g=of[:, 3].copy(), dc=of[:, 4:7].copy(), visible=oi[:, 1] != 0)
 
     def free(self) -> None:
         if self._h:

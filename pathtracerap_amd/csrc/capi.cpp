@@ -4,6 +4,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/pathtracer_amd.h"
 #include "renderer.h"
@@ -494,6 +495,42 @@ int pt_renderer_hit_albedo(pt_renderer* r, int n, const float* orig, const float
     R_CALL(r->r->hitAlbedo(n, orig, dir, dist, model, tri, rgb_out));
 }
 
+static_assert(PT_LIGHT_FLOATS == pt::kLightFloats, "PT_LIGHT_FLOATS is the light record's size");
+int pt_renderer_set_direct_light(pt_renderer* r, int on) { R_CALL(r->r->setDirectLight(on)); }
+int pt_renderer_direct_light(pt_renderer* r, int* on, int* n_lights, float* area) {
+    R_CALL(r->r->directLight(on, n_lights, area));
+}
+int pt_scene_lights(const pt_scene* s, int max_lights, float* recs_out, float* area_total) {
+    if (!s) return set_err("null scene");
+    std::vector<float> recs;
+    double area = 0.0;
+    const int n = s->s.lightTable(recs, &area, nullptr);
+    if (recs_out && max_lights > 0)
+        std::memcpy(recs_out, recs.data(), (size_t)(n < max_lights ? n : max_lights) * pt::kLightFloats * sizeof(float));
+    if (area_total) *area_total = (float)area;
+    return n;
+}
+int pt_renderer_lights(pt_renderer* r, int max_lights, float* recs_out, float* area_total) {
+    if (!r || !r->r) return set_err("null renderer");
+    if (area_total) r->r->directLight(nullptr, nullptr, area_total);
+    return r->r->lights(recs_out, max_lights);
+}
+int pt_scene_direct_light(const pt_scene* s) {
+    if (!s) return set_err("null scene");
+    return s->s.settings.direct_light ? 1 : 0;
+}
+int pt_renderer_occluded(pt_renderer* r, int n, const float* orig, const float* target, int* out) {
+    if (n < 0 || (n > 0 && (!orig || !target || !out))) return set_err("pt_renderer_occluded: bad arguments");
+    R_CALL(r->r->occludedSegments(n, orig, target, out));
+}
+int pt_renderer_direct_sample(pt_renderer* r, int n, const float* orig, const float* dir, const float* dist,
+                              const int* model, const int* tri, const float* color, const int* ids, float* out_f,
+                              int* out_i) {
+    if (n < 0 || (n > 0 && (!orig || !dir || !dist || !model || !tri || !color || !ids || !out_f || !out_i)))
+        return set_err("pt_renderer_direct_sample: bad arguments");
+    R_CALL(r->r->directSample(n, orig, dir, dist, model, tri, color, ids, out_f, out_i));
+}
+
 int pt_environment_sky(const float zenith[3], const float horizon[3], const float ground[3], int n, float* texels_out) {
     if (!zenith || !horizon || !ground || !texels_out) return set_err("environment_sky: null argument");
     if (n < 1 || n > pt::kEnvMaxN) return set_err("environment_sky: n must be 1 .. 2048");
@@ -608,6 +645,10 @@ int pt_render(const char* scene_config, const pt_render_config* cfg, const char*
     const int has_cam = rc >= 0 ? pt_scene_camera(s, c.width, c.height, &cam) : 0;
     if (has_cam < 0) rc = -1;
     if (rc >= 0 && has_cam > 0) rc = pt_renderer_set_camera(r, &cam);
+    if (rc >= 0 && pt_scene_direct_light(s) > 0) {       // the RENDER block's direct_light: 1 (it implies moments)
+        rc = pt_renderer_enable_moments(r, nullptr);
+        if (rc >= 0) rc = pt_renderer_set_direct_light(r, 1);
+    }
     if (rc >= 0) rc = pt_renderer_allocate_on_gpu(r, s);
     if (rc >= 0) rc = pt_renderer_render_loop(r, 0, c.iterations);
     if (rc >= 0) rc = pt_renderer_synchronize(r);

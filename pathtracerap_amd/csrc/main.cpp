@@ -43,6 +43,10 @@
 // the filter's guides are the means of the samples' own first hits (pt_renderer_enable_guides,
 // PT_DENOISE_SAMPLED_GUIDES); it needs --jitter or a lens, whose iterations accumulate them.
 //
+// --direct-light: direct lighting (pt_renderer_set_direct_light): every diffuse hit samples the
+// lights through a shadow ray.  It implies the moments; the scene file's RENDER key
+// direct_light: 1 does the same.
+//
 // Default: PT_ACCEL_GRID_FAST (the reference grid's image, bit for bit) with 16
 // iterations in flight, each on its own HIP stream and hardware queue.
 #include <chrono>
@@ -62,7 +66,7 @@ int main(int argc, char** argv) {
                              "[--grid|--grid-fast|--bvh] [--pipelines P] [--noise-target X [--check-every N]] "
                              "[--denoise [--denoise-passes N]] [--denoise-albedo] [--denoise-guides] [--adaptive X [--check-every N] [--min-iter N]] "
                              "[--jitter WIDTH] [--look-from X Y Z --look-at X Y Z [--up X Y Z] [--fov DEG] "
-                             "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth]\n", argv[0]);
+                             "[--focus D] [--lens R]] [--sky ZR ZG ZB HR HG HB [--ground R G B]] [--smooth] [--direct-light]\n", argv[0]);
         return 2;
     }
     pt_render_config cfg;
@@ -84,6 +88,7 @@ int main(int argc, char** argv) {
     double fov = 45.0, focus = 0.0, lens = 0.0;       // no --focus: the distance from eye to target
     auto vec3 = [&](double* v, int& i) { for (int k = 0; k < 3; k++) v[k] = std::atof(argv[++i]); };
     bool sky = false, has_ground = false, smooth = false;
+    bool direct = pt_scene_direct_light(s) > 0;
     double zenith[3] = {0, 0, 0}, horizon[3] = {0, 0, 0}, ground[3] = {0, 0, 0};
     pt_denoise_params dn;
     pt_default_denoise_params(&dn);
@@ -109,6 +114,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sky") && i + 6 < argc) { vec3(zenith, i); vec3(horizon, i); sky = true; }
         else if (!std::strcmp(argv[i], "--ground") && i + 3 < argc) { vec3(ground, i); has_ground = true; }
         else if (!std::strcmp(argv[i], "--smooth")) smooth = true;
+        else if (!std::strcmp(argv[i], "--direct-light")) direct = true;
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-albedo")) { denoise = true; denoise_flags |= PT_DENOISE_DEMODULATE; }
         else if (!std::strcmp(argv[i], "--denoise-guides")) { denoise = true; denoise_flags |= PT_DENOISE_SAMPLED_GUIDES; }
@@ -148,8 +154,8 @@ int main(int argc, char** argv) {
     if (smooth && pt_scene_set_model_smooth(s, -1, 1) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     if (pt_scene_build(s, cfg.grid, cfg.accel != PT_ACCEL_GRID) < 0) { std::fprintf(stderr, "%s\n", pt_last_error()); return 1; }
     pt_renderer* r = pt_renderer_create(&cfg);
-    if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0) && pt_renderer_enable_moments(r, nullptr) < 0) ||
-        (guides && pt_renderer_enable_guides(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
+    if (!r || ((noise_target >= 0 || denoise || adaptive_target >= 0 || direct) && pt_renderer_enable_moments(r, nullptr) < 0) ||
+        (direct && pt_renderer_set_direct_light(r, 1) < 0) || (guides && pt_renderer_enable_guides(r, nullptr) < 0) || pt_renderer_allocate_on_gpu(r, s) < 0) {
         std::fprintf(stderr, "%s\n", pt_last_error());
         return 1;
     }

@@ -19,6 +19,7 @@ constexpr float kFMax = 9999999.0f;
 constexpr float kFMin = -9999990.0f;
 // utility.h:20-22
 constexpr float kTwoPi = 6.2831853071795864769252867665590057683943f;
+constexpr float kPi = 3.1415926535897932384626433832795028841972f;
 constexpr float kSqrtOneThird = 0.5773502691896257645091487805019574556476f;
 
 // Primitive.h:70-79 Material::MaterialType

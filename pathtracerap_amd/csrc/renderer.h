@@ -248,6 +248,18 @@ public:
     int enableGuides(float* device_g);               // before allocateOnGPU; null: own buffer
     int readGuides(float* host_g);                   // W*H*8 floats
     int guideCounts(int* tile_counts_host);          // returns the tile count
+    // Direct lighting (no counterpart in the reference): while on, every MAT_DIFFUSE hit of a live
+    // ray samples one point of one EMISSIVE triangle and traces a shadow ray (k_direct), and an
+    // EMISSIVE hit directly after a DIFFUSE vertex counts nothing.  Before or after allocateOnGPU;
+    // a change after it starts a new render.  Needs moments, the split trace and max_bounces <= 63
+    int setDirectLight(int on);
+    int directLight(int* on, int* n_lights, float* area) const;
+    // the allocation's light table: kLightFloats floats per light (Scene::lightTable); returns the count
+    int lights(float* recs_out, int max_lights) const;
+    // test hooks: segment visibility (1: occluded) and the light sample of caller-given hits
+    int occludedSegments(int n, const float* orig, const float* target, int* out);
+    int directSample(int n, const float* orig, const float* dir, const float* dist, const int* model, const int* tri,
+                     const float* color, const int* ids, float* out_f, int* out_i);
 
     RenderConfig cfg;
     std::string last_error;
@@ -283,6 +295,11 @@ private:
     int launchGuideFirst(const KParams& k, int q, hipStream_t st);
     int launchMergeGuides(int q, hipStream_t st, const unsigned char* tile_mask);
     int allocDenoise();
+    int directRefusal(bool need_moments);              // direct lighting cannot run as configured: last_error says why
+    int ensureDirect();                  // the device table and the per-pipeline state, once per allocation
+    bool directActive() const { return direct_on && direct_ready; }
+    int launchDirect(const KParams& k, int q, hipStream_t st, bool first, int iter, int b, const unsigned char* tile_mask);
+    int launchDirectResolve(int q, hipStream_t st);
     int writeBmp(const std::string& path, const float* rgb, float div);     // Renderer.cpp:15-63
 
     KParams kp{};                   // pipeline 0 (and everything the pipelines share)
@@ -312,6 +329,14 @@ private:
     float* guides = nullptr;         // W*H*8 sums G
     float* guide_contrib[kMaxPipes]{};   // pipeline i's per-iteration records (k_guide_first -> k_merge_guides)
     std::vector<int> guide_tile_counts;  // generated samples per noise tile since allocateOnGPU / clearImage (host)
+    bool direct_on = false;              // setDirectLight
+    bool direct_ready = false;           // the allocation has lights and their device state exists
+    bool direct_textured = false;        // the allocation's scene has a textured EMISSIVE model (refused)
+    std::vector<float> light_recs;       // the allocation's light table (host), kLightFloats floats per light
+    double light_area = 0.0;             // A_total
+    float4* lights_dev = nullptr;
+    float* direct_D[kMaxPipes]{};        // pipeline i's direct light of the iteration in flight, 3 floats per pixel
+    unsigned char* direct_flags[kMaxPipes]{};    // ... and its flag byte per pixel
     double* noise_sum = nullptr;     // noise(): per-tile sums, then the mean
     float* noise_err = nullptr;      // per-tile errors, then the largest
     int samples_accumulated = 0;     // iterations enqueued since allocateOnGPU / clearImage

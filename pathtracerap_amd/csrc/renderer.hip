@@ -13,6 +13,8 @@
 //              the map the scatter wrote, else via the scan), shade, compact /
 //              accumulate
 //              (PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0: the fused k_bounce<rest, accel>)
+//   direct lighting (pt_renderer_set_direct_light): k_direct before every k_bounce samples
+//              the lights at the bounce's diffuse hits, k_direct_resolve ends the iteration
 // Iterations run `pipelines` at a time on their own streams (Renderer::renderLoop);
 // with more than one, terminated rays write a per-pipeline contribution buffer
 // that k_merge adds to the image in iteration order.
@@ -3345,6 +3347,223 @@ __global__ __launch_bounds__(256) void k_selftest_dielectric(int n, const float*
 }
 
 // ---------------------------------------------------------------------------
+// Direct lighting (pt_renderer_set_direct_light; include/pathtracer_amd.h, "Direct lighting",
+// states the estimator operation by operation; no counterpart in the reference).  New kernels
+// only, defined after every other kernel, so that those keep their places in the code object.
+// ---------------------------------------------------------------------------
+
+// Any-hit query: does some triangle of some model that tri_test_rec accepts lie at a world
+// distance (model_hit_dist) below tmax along (orig, dirn)?  The decision is ACCEL_BVH's for every
+// accel: the model-space ray, the triangle test and the distance are intersect_scene_g's values,
+// so an accepted triangle here is one the closest-hit query accepts with the same distance.
+// Per model: model_culled<ACCEL_BVH> with gdist = tmax, then the 4-wide BLAS with a leaf functor
+// that aborts at the first such triangle.  Nodes are pruned against a model-space image of tmax:
+// a world distance s along the ray is the model parameter s * stretch exactly (the map is affine),
+// and the slack (0.1 % and 0.01 world units) covers model_hit_dist's rounding; pruning is
+// conservative, the decision exact.  One lane per ray, lane-contiguous LDS stack (kStack * STRIDE).
+template <int STRIDE>
+__device__ bool occluded(const KParams& p, f3 orig, f3 dirn, float tmax, int* __restrict__ stack) {
+    const f3 winv = node_inv(cull_inv(dirn));
+    const float dlen = sqrtf(dot(dirn, dirn));
+    for (int im = 0; im < p.nmodels; im++) {
+        const ModelRec& M = p.models[im];
+        if (model_culled<ACCEL_BVH>(M, orig, dirn, winv, dlen, tmax)) continue;
+        const f3 o = xform12(M.w2m, orig, 1.0f);
+        const f3 dm = xform12(M.w2m, dirn, 0.0f);
+        const f3 d = normalize(dm);
+        const f3 inv = mk3(1 / d.x, 1 / d.y, 1 / d.z);
+        const float stretch = sqrtf(dot(dm, dm)) / dlen;
+        const float bd = (tmax * 1.001f + 0.01f) * stretch + 1e-3f;
+        bool found = false;
+        unsigned n_nodes = 0;
+        auto leaf = [&](int first, int count) {
+            for (int i = first; i < first + count; i++) {
+                const float4 A = p.bvh_tri_geom[3 * i], B = p.bvh_tri_geom[3 * i + 1], C = p.bvh_tri_geom[3 * i + 2];
+                float t;
+                if (tri_test_rec(A, B, C, o, d, t) && model_hit_dist(M, o, d, t, orig) < tmax) {
+                    found = true;
+                    return false;
+                }
+            }
+            return true;
+        };
+        bvh4_traverse<STRIDE>(p, M, o, node_inv(inv), stack, leaf, [&] { return bd; }, n_nodes);
+        if (found) return true;
+    }
+    return false;
+}
+
+// The light table (Renderer::allocateOnGPU): kLightRec float4 per light -- (p0, area),
+// (e1, model), (e2, cdf), (nl, -), (emission, -), world space -- and the per-pipeline state:
+// D, 3 floats per pixel, and one flag byte per pixel (bit 0: the previous vertex sampled a light,
+// bit 1: suppress the terminal).  A kernel argument of its own: KParams stays as it is.
+constexpr int kLightRec = 5;
+struct DirectArgs {
+    const float4* lights;
+    int n_lights;
+    float a_total;
+    float* D;
+    unsigned char* flags;
+};
+
+// One light sample for the hit of ray (o, d) at distance dist, with the shading normal n, the
+// albedo mc and the ray's colour c: section "Direct lighting" of the header, in its order.
+// light < 0: nothing was sampled (the geometry test failed) and no shadow ray was traced.
+struct DirectSample { int light; f3 y; float g; f3 dc; int visible; };
+template <int STRIDE>
+__device__ __forceinline__ DirectSample direct_sample(const KParams& p, const DirectArgs& a, f3 o, f3 d, float dist, f3 n,
+                                                      f3 mc, f3 c, int iter, int slot, int bounces, int* stack) {
+    DirectSample s;
+    s.light = -1; s.y = mk3(0, 0, 0); s.g = 0.0f; s.dc = mk3(0, 0, 0); s.visible = 0;
+    Rng r0 = Rng::make(iter, slot, 256 + bounces), r1 = Rng::make(iter, slot, 320 + bounces),
+        r2g = Rng::make(iter, slot, 384 + bounces);
+    const float u0 = r0.u01(), u1 = r1.u01(), u2 = r2g.u01();
+    int lo = 0, hi = a.n_lights - 1;            // the smallest i with u0 < cdf[i], else the last light
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u0 < a.lights[kLightRec * mid + 2].w) hi = mid; else lo = mid + 1;
+    }
+    const float4 L0 = a.lights[kLightRec * lo], L1 = a.lights[kLightRec * lo + 1], L2 = a.lights[kLightRec * lo + 2],
+                 L3 = a.lights[kLightRec * lo + 3], L4 = a.lights[kLightRec * lo + 4];
+    const float sq = sqrtf(u1);
+    const float a1 = sq * (1.0f - u2), a2 = sq * u2;
+    const f3 y = (mk3(L0.x, L0.y, L0.z) + mk3(L1.x, L1.y, L1.z) * a1) + mk3(L2.x, L2.y, L2.z) * a2;
+    const f3 dir = normalize(d);
+    const f3 ip = o + dir * dist;
+    const f3 xo = ip + n * 0.1f;
+    const f3 w = y - xo;
+    const float r2 = dot(w, w);
+    const float r = sqrtf(r2);
+    const f3 wn = normalize(w);
+    const float cx = dot(n, wn);
+    const float cy = fabsf(dot(mk3(L3.x, L3.y, L3.z), wn));
+    if (!((cx > 0.0f) && (cy > 0.0f) && (r2 > 0.0f))) return s;      // a NaN fails the test
+    s.light = lo;
+    s.y = y;
+    s.g = ((cx * cy) / (kPi * r2)) * a.a_total;
+    s.dc = ((c * mc) * mk3(L4.x, L4.y, L4.z)) * s.g;
+    s.visible = occluded<STRIDE>(p, xo, wn, r * 0.999f, stack) ? 0 : 1;
+    return s;
+}
+
+// One lane per live slot of bounce `bounce`, between that bounce's trace and its k_bounce: the
+// light sample of every MAT_DIFFUSE hit, added to the pixel's D, and the pixel's flags.
+// FIRST: the cached primary hits of an ungenerated iteration (slot = pixel index; tile_mask null
+// or the iteration's mask: a pixel of an inactive tile does nothing).  Otherwise the slot's ray is
+// found as k_trace_deferred finds it (slot_src when the bounce was sorted, else the blk_off
+// search) and the hit is the record the shading pass reads, with its normal and its albedo.
+// iter < 0: the id is read from iter_dev (graph replay).  Work is sized from n_live on the device;
+// idle blocks return.  Plain loads and stores: a pixel owns one ray per iteration and pipeline,
+// and the kernels of a pipeline are stream-ordered.
+template <bool FIRST, int BS>
+__global__ __launch_bounds__(BS) void k_direct(KParams p, DirectArgs a, int iter, int bounce,
+                                               const unsigned char* __restrict__ tile_mask, int tiles_x) {
+    __shared__ int s_stack[kStack * BS];
+    const int n = FIRST ? p.npix : p.n_live[bounce];
+    const int j = blockIdx.x * BS + threadIdx.x;
+    if (j >= n) return;
+    RayState r;
+    Hit h;
+    int tri = kTriCached;
+    if (FIRST) {
+        if (tile_mask && !tile_active(tile_mask, tiles_x, p.width, j)) return;
+        first_hit_state(p, j, r, h);
+    } else {
+        const int src = p.slot_src ? p.slot_src[j] : slot_source(p, j);
+        r = load_ray(p, (bounce + 1) & 1, src);
+        h = get_hit(p, j, r.o, r.d);
+        tri = __float_as_int(p.hit4[j].y);
+    }
+    if ((unsigned)r.pixel >= (unsigned)p.npix) return;      // never: every pool ray carries a launched pixel
+    if (!(h.dist < kFMax) || h.model < 0 || r.bounces <= 0) return;     // a miss ends the path: its flags are not read again
+    const ModelShade& S = p.shade[h.model];
+    const int mt = S.mat_type;
+    unsigned f = a.flags[r.pixel];
+    if (mt == MAT_EMISSIVE && (f & 1u)) f |= 2u;
+    f = (f & ~1u) | (mt == MAT_DIFFUSE ? 1u : 0u);
+    a.flags[r.pixel] = (unsigned char)f;
+    if (mt != MAT_DIFFUSE) return;
+    f3 mc = mk3(S.color[0], S.color[1], S.color[2]);
+    if (p.tex) {
+        if (FIRST) {
+            const float4 ca = p.cache_albedo[j];
+            mc = mk3(ca.x, ca.y, ca.z);
+        } else {
+            mc = hit_albedo(p, r.o, r.d, h.dist, h.model, tri);
+        }
+    }
+    const DirectSample s = direct_sample<BS>(p, a, r.o, r.d, h.dist, h.n, mc, r.c, iter >= 0 ? iter : *p.iter_dev, j,
+                                             r.bounces, s_stack + threadIdx.x);
+    if (s.light >= 0 && s.visible) {
+        float* dp = a.D + 3 * (size_t)r.pixel;
+        dp[0] += s.dc.x;
+        dp[1] += s.dc.y;
+        dp[2] += s.dc.z;
+    }
+}
+
+// Once per iteration, after the last k_scan and before the merge: the pipeline's contribution
+// buffer becomes the sample of the header's section, and D and the flags return to zero.  A pixel
+// without direct light and without a suppressed terminal is left as it is.
+__global__ __launch_bounds__(256) void k_direct_resolve(float* __restrict__ contrib, float* __restrict__ D,
+                                                        unsigned char* __restrict__ flags, int npix) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned f = flags[i];
+    float* dp = D + 3 * (size_t)i;
+    const float d0 = dp[0], d1 = dp[1], d2 = dp[2];
+    if (f == 0 && d0 == 0.0f && d1 == 0.0f && d2 == 0.0f) return;
+    float* cp = contrib + 3 * (size_t)i;
+    const bool sup = (f & 2u) != 0;
+    const float t0 = sup ? 0.0f : cp[0], t1 = sup ? 0.0f : cp[1], t2 = sup ? 0.0f : cp[2];
+    cp[0] = d0 == 0.0f ? t0 : sqrtf(t0 * t0 + d0);
+    cp[1] = d1 == 0.0f ? t1 : sqrtf(t1 * t1 + d1);
+    cp[2] = d2 == 0.0f ? t2 : sqrtf(t2 * t2 + d2);
+    dp[0] = 0.0f; dp[1] = 0.0f; dp[2] = 0.0f;
+    flags[i] = 0;
+}
+
+// Test hook (pt_renderer_occluded): caller-given segments, one lane each.  The shadow ray of
+// orig -> target: direction normalize(target - orig), tmax = 0.999 * |target - orig|; a segment
+// of zero length reads unoccluded.
+__global__ __launch_bounds__(kBlock) void k_occluded(KParams p, int n, const float* orig, const float* target, int* out) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const f3 o = mk3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]);
+    const f3 w = mk3(target[3 * i], target[3 * i + 1], target[3 * i + 2]) - o;
+    const float r2 = dot(w, w);
+    int occ = 0;
+    if (r2 > 0.0f) occ = occluded<kBlock>(p, o, normalize(w), sqrtf(r2) * 0.999f, s_stack + threadIdx.x) ? 1 : 0;
+    out[i] = occ;
+}
+
+// Test hook (pt_renderer_direct_sample): direct_sample for caller-given hits (ray, distance,
+// model, triangle), colours and seeds, with the normal and the albedo the shading pass uses for
+// such a hit.  Ranges are checked by the host.  out_f: 8 floats per hit (y, g, dc, -); out_i: the
+// light (-1: none) and the visibility flag.
+__global__ __launch_bounds__(kBlock) void k_direct_sample(KParams p, DirectArgs a, int n, const float* orig, const float* dir,
+                                                          const float* dist, const int* model, const int* tri,
+                                                          const float* color, const int* ids, float* out_f, int* out_i) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const f3 o = mk3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]), d = mk3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+    const int m = model[i], t = tri[i];
+    const float4 tn = p.tri_normal[t];
+    const f3 g = normalize(xform_normal9(p.models[m].nm, mk3(tn.x, tn.y, tn.z)));       // get_hit's flat normal
+    const f3 nn = shading_normal(p, o, d, dist[i], m, t, g);
+    const f3 mc = hit_albedo(p, o, d, dist[i], m, t);
+    const DirectSample s = direct_sample<kBlock>(p, a, o, d, dist[i], nn, mc, mk3(color[3 * i], color[3 * i + 1], color[3 * i + 2]),
+                                                 ids[3 * i], ids[3 * i + 1], ids[3 * i + 2], s_stack + threadIdx.x);
+    float* of = out_f + 8 * (size_t)i;
+    of[0] = s.y.x; of[1] = s.y.y; of[2] = s.y.z; of[3] = s.g;
+    of[4] = s.dc.x; of[5] = s.dc.y; of[6] = s.dc.z; of[7] = 0.0f;
+    out_i[2 * i] = s.light;
+    out_i[2 * i + 1] = s.visible;
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 Renderer::Renderer(const RenderConfig& c) : cfg(c) {}
@@ -3434,6 +3653,20 @@ int Renderer::allocateOnGPU(const Scene& scene) {
         last_error = "guides need the split trace, whose hit records they read: ACCEL_GRID_FAST or ACCEL_BVH without "
                      "PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0";
         return -1;
+    }
+    // direct lighting: the scene's light table stays on the host whether or not the feature is on
+    // (setDirectLight may follow the allocation); its device copy and the per-pipeline state
+    // exist only while it is on and the scene has a light
+    {
+        std::vector<float> recs;
+        double area = 0.0;
+        bool textured = false;
+        scene.lightTable(recs, &area, &textured);
+        const bool was = direct_textured;
+        direct_textured = textured;
+        if (direct_on && directRefusal(true) != 0) { direct_textured = was; return -1; }
+        light_recs.swap(recs);
+        light_area = area;
     }
     freeBuffers();
     if (!stream_set && !stream) {
@@ -3706,6 +3939,7 @@ int Renderer::allocateOnGPU(const Scene& scene) {
     kp = pk[0];
     if (moments_on && allocMoments() != 0) return -1;
     if (guides_on && allocGuides() != 0) return -1;
+    if (direct_on && ensureDirect() != 0) return -1;
     PT_HIP(hipStreamSynchronize(stream));
     const char* gr = std::getenv("PT_GRAPH");
     use_graph = gr && std::atoi(gr) != 0;
@@ -4069,9 +4303,13 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, cons
             // sampled guides: pass 1's hit records, before its shading pass writes pool 1 and its
             // scan the offsets (outside the event pairs: the kernel groups keep their meaning)
             if (b == 1 && jitter && guides_on && launchGuideFirst(ku, q, st) != 0) return -1;
+            // direct lighting: this bounce's hits sample the lights before the shading pass moves the rays
+            if (directActive() && launchDirect(ku, q, st, false, iter, b, nullptr) != 0) return -1;
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             launchBounce(ku, st, false, grid, iter, b, kAccelHitBuffer);
         } else {
+            // ... and the cached primary hits of an ungenerated iteration (bounce 0 traces nothing)
+            if (b == 0 && !jitter && directActive() && launchDirect(k, q, st, true, iter, 0, tile_mask) != 0) return -1;
             if (pall) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); }
             if (b == 0 && jitter && k.camera) launchGenCamera(k, st, iter, tile_mask);
             else if (b == 0 && jitter) launchGenJitter(k, st, iter, tile_mask);
@@ -4089,7 +4327,169 @@ int Renderer::enqueueIteration(int q, hipStream_t st, int iter, int passes, cons
         PT_HIP(hipGetLastError());
         if (pall) { hipEventRecord(e1, st); scan_events.push_back({e0, e1}); }
     }
+    // direct lighting: the contribution buffer becomes the iteration's sample (inside a captured graph too)
+    if (directActive() && launchDirectResolve(q, st) != 0) return -1;
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Direct lighting: host side
+// ---------------------------------------------------------------------------
+int Renderer::directRefusal(bool need_moments) {
+    if (cfg.accel == ACCEL_GRID || !splitTraceWanted()) {
+        last_error = "direct light needs the split trace, whose hit records it reads: ACCEL_GRID_FAST or ACCEL_BVH without "
+                     "PT_GF_SPLIT=0 / PT_TRACE_SPLIT=0";
+        return -1;
+    }
+    if (cfg.max_bounces > 63) {
+        last_error = "direct light needs max_bounces <= 63 (its draws seed with depths 256 + bounces .. 384 + bounces)";
+        return -1;
+    }
+    if (need_moments && !moments_on) {
+        last_error = "direct light needs moments (call pt_renderer_enable_moments before allocate_on_gpu)";
+        return -1;
+    }
+    if (direct_textured) {
+        last_error = "direct light: an EMISSIVE model has a texture (emission textures are not supported)";
+        return -1;
+    }
+    return 0;
+}
+
+int Renderer::ensureDirect() {
+    if (direct_ready || light_recs.empty() || !(light_area > 0.0)) return 0;     // no light: nothing is launched
+    const size_t nl = light_recs.size() / kLightFloats;
+    static_assert(kLightFloats == 4 * kLightRec, "a light record is kLightRec float4");
+    PT_HIP(upload(allocs, &lights_dev, light_recs.data(), nl * kLightFloats * sizeof(float), stream));
+    const size_t npix_all = (size_t)cfg.width * cfg.height;
+    for (int i = 0; i < npipes; i++) {
+        PT_HIP(upload(allocs, &direct_D[i], nullptr, npix_all * 3 * sizeof(float), stream));
+        PT_HIP(hipMemsetAsync(direct_D[i], 0, npix_all * 3 * sizeof(float), stream));
+        PT_HIP(upload(allocs, &direct_flags[i], nullptr, npix_all, stream));
+        PT_HIP(hipMemsetAsync(direct_flags[i], 0, npix_all, stream));
+    }
+    PT_HIP(hipStreamSynchronize(stream));      // light_recs is pageable
+    direct_ready = true;
+    return 0;
+}
+
+int Renderer::setDirectLight(int on) {
+    const bool want = on != 0;
+    if (want == direct_on) return 0;
+    if (want && directRefusal(allocated) != 0) return -1;     // before allocateOnGPU moments may still be enabled
+    if (allocated) {
+        // as setEnvironment: everything enqueued finishes, captured launches hold the old loop
+        PT_HIP(hipStreamSynchronize(stream));
+        for (int i = 1; i < npipes; i++) PT_HIP(hipStreamSynchronize(pstream[i]));
+        dropGraphs();
+    }
+    direct_on = want;
+    if (!allocated) return 0;
+    if (want && ensureDirect() != 0) { direct_on = false; return -1; }
+    return clearImage();                             // a new estimator is a new render
+}
+
+int Renderer::directLight(int* on, int* n_lights, float* area) const {
+    if (on) *on = direct_on ? 1 : 0;
+    if (n_lights) *n_lights = allocated ? (int)(light_recs.size() / kLightFloats) : 0;
+    if (area) *area = allocated ? (float)light_area : 0.0f;
+    return 0;
+}
+
+int Renderer::lights(float* recs_out, int max_lights) const {
+    const int n = allocated ? (int)(light_recs.size() / kLightFloats) : 0;
+    if (recs_out)
+        std::memcpy(recs_out, light_recs.data(), (size_t)std::max(0, std::min(n, max_lights)) * kLightFloats * sizeof(float));
+    return n;
+}
+
+// k_direct on pipeline q for bounce b (k: the parameters that bounce's trace ran with, its slot map
+// or none); one lane per launched pixel, the lanes beyond n_live[b] leave at once.
+int Renderer::launchDirect(const KParams& k, int q, hipStream_t st, bool first, int iter, int b,
+                           const unsigned char* tile_mask) {
+    const DirectArgs a{lights_dev, (int)(light_recs.size() / kLightFloats), (float)light_area, direct_D[q], direct_flags[q]};
+    const dim3 grid((unsigned)((k.npix + 63) / 64));
+    if (first) hipLaunchKernelGGL((k_direct<true, 64>), grid, dim3(64), 0, st, k, a, iter, b, tile_mask, noiseTilesX());
+    else hipLaunchKernelGGL((k_direct<false, 64>), grid, dim3(64), 0, st, k, a, iter, b, tile_mask, noiseTilesX());
+    PT_HIP(hipGetLastError());
+    return 0;
+}
+
+int Renderer::launchDirectResolve(int q, hipStream_t st) {
+    const int npix_all = cfg.width * cfg.height;
+    hipLaunchKernelGGL(k_direct_resolve, dim3((unsigned)((npix_all + 255) / 256)), dim3(256), 0, st, pk[q].contrib, direct_D[q],
+                       direct_flags[q], npix_all);
+    PT_HIP(hipGetLastError());
+    return 0;
+}
+
+int Renderer::occludedSegments(int n, const float* orig, const float* target, int* out) {
+    if (!allocated) { last_error = "occluded: not allocated"; return -1; }
+    if (!kp.bvh4) { last_error = "occluded: the scene has no BLAS (accel grid)"; return -1; }
+    if (n <= 0) return 0;
+    float* d_buf = nullptr;                         // orig 3n, target 3n, out n
+    PT_HIP(hipMalloc(&d_buf, (size_t)n * 28));
+    float* d_o = d_buf;
+    float* d_t = d_buf + 3 * (size_t)n;
+    int* d_out = reinterpret_cast<int*>(d_buf + 6 * (size_t)n);
+    hipError_t e = hipMemcpyAsync(d_o, orig, (size_t)n * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_t, target, (size_t)n * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_occluded, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, kp, n, d_o, d_t, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    hipFree(d_buf);
+    if (e != hipSuccess) return fail(e, "occluded");
+    return checkFaults();
+}
+
+int Renderer::directSample(int n, const float* orig, const float* dir, const float* dist, const int* model, const int* tri,
+                           const float* color, const int* ids, float* out_f, int* out_i) {
+    if (!allocated) { last_error = "direct_sample: not allocated"; return -1; }
+    if (!directActive()) { last_error = "direct_sample: direct light is off or the scene has no light"; return -1; }
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; i++) {                   // refused before any launch: the kernel indexes with these
+        if (model[i] < 0 || model[i] >= kp.nmodels) { last_error = "direct_sample: model index out of range"; return -1; }
+        if (tri[i] < 0 || tri[i] >= alloc_ntris) { last_error = "direct_sample: triangle index out of range"; return -1; }
+        if (ids[3 * i] < 0 || ids[3 * i + 1] < 0 || ids[3 * i + 2] < 0 || ids[3 * i + 2] > 63) {
+            last_error = "direct_sample: ids are (iteration >= 0, slot >= 0, bounces in 0 .. 63)";
+            return -1;
+        }
+    }
+    // orig 3n, dir 3n, dist n, model n, tri n, color 3n, ids 3n, out_f 8n, out_i 2n
+    float* d_buf = nullptr;
+    PT_HIP(hipMalloc(&d_buf, (size_t)n * 25 * 4));
+    const size_t N = (size_t)n;
+    float* d_o = d_buf;
+    float* d_d = d_buf + 3 * N;
+    float* d_t = d_buf + 6 * N;
+    int* d_m = reinterpret_cast<int*>(d_buf + 7 * N);
+    int* d_tri = reinterpret_cast<int*>(d_buf + 8 * N);
+    float* d_c = d_buf + 9 * N;
+    int* d_ids = reinterpret_cast<int*>(d_buf + 12 * N);
+    float* d_of = d_buf + 15 * N;
+    int* d_oi = reinterpret_cast<int*>(d_buf + 23 * N);
+    hipError_t e = hipMemcpyAsync(d_o, orig, N * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d, dir, N * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_t, dist, N * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_m, model, N * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tri, tri, N * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_c, color, N * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, N * 12, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        const DirectArgs a{lights_dev, (int)(light_recs.size() / kLightFloats), (float)light_area, nullptr, nullptr};
+        hipLaunchKernelGGL(k_direct_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, kp, a, n, d_o,
+                           d_d, d_t, d_m, d_tri, d_c, d_ids, d_of, d_oi);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_f, d_of, N * 32, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_i, d_oi, N * 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    hipFree(d_buf);
+    if (e != hipSuccess) return fail(e, "direct_sample");
+    return checkFaults();
 }
 
 void Renderer::dropGraphs() {
@@ -4619,6 +5019,9 @@ void Renderer::freeBuffers() {
     m2 = nullptr;
     guides = nullptr;
     for (int i = 0; i < kMaxPipes; i++) guide_contrib[i] = nullptr;
+    direct_ready = false;
+    lights_dev = nullptr;
+    for (int i = 0; i < kMaxPipes; i++) { direct_D[i] = nullptr; direct_flags[i] = nullptr; }
     noise_sum = nullptr;
     noise_err = nullptr;
     dn_cv[0] = dn_cv[1] = dn_nd = nullptr;

@@ -339,6 +339,55 @@ float Scene::modelIor(int model) const {
     return models[model].ior;
 }
 
+int Scene::lightTable(std::vector<float>& recs, double* area_total, bool* textured) const {
+    recs.clear();
+    if (textured) *textured = false;
+    std::vector<double> areas;
+    double total = 0.0;
+    for (size_t im = 0; im < models.size(); im++) {
+        const Model& m = models[im];
+        if (m.mat.material_type != MAT_EMISSIVE) continue;
+        if (textured && m.texture >= 0) *textured = true;
+        const float* M = m.model_to_world;
+        const IndexRange& tr = meshes[m.mesh_index].triangle_indices;
+        for (int t = tr.start_index; t < tr.end_index; t++) {
+            double pw[3][3];
+            for (int j = 0; j < 3; j++) {
+                const f3 v = vertices[triangles[t].vertex_indices[j]].position;
+                for (int k = 0; k < 3; k++)
+                    pw[j][k] = (((double)M[k] * v.x + (double)M[4 + k] * v.y) + (double)M[8 + k] * v.z) + (double)M[12 + k];
+            }
+            double e1[3], e2[3];
+            for (int k = 0; k < 3; k++) { e1[k] = pw[1][k] - pw[0][k]; e2[k] = pw[2][k] - pw[0][k]; }
+            const double cr[3] = {e1[1] * e2[2] - e2[1] * e1[2], e1[2] * e2[0] - e2[2] * e1[0], e1[0] * e2[1] - e2[0] * e1[1]};
+            const double len = std::sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
+            const double area = 0.5 * len;
+            float r[kLightFloats] = {};
+            int mi = (int)im;
+            for (int k = 0; k < 3; k++) {
+                r[k] = (float)pw[0][k];
+                r[4 + k] = (float)e1[k];
+                r[8 + k] = (float)e2[k];
+                r[12 + k] = len > 0.0 ? (float)(cr[k] / len) : 0.0f;
+                r[16 + k] = m.mat.color[k];
+            }
+            r[3] = (float)area;
+            std::memcpy(&r[7], &mi, sizeof mi);
+            recs.insert(recs.end(), r, r + kLightFloats);
+            areas.push_back(area);
+            total += area;
+        }
+    }
+    double acc = 0.0;
+    for (size_t i = 0; i < areas.size(); i++) {
+        acc += areas[i];
+        recs[i * kLightFloats + 11] = total > 0.0 ? (float)(acc / total) : 0.0f;
+    }
+    if (!areas.empty()) recs[(areas.size() - 1) * kLightFloats + 11] = 1.0f;
+    if (area_total) *area_total = total;
+    return (int)areas.size();
+}
+
 int Scene::setMeshUv(int mesh, const float* uv, int nv) {
     if (mesh < 0 || mesh >= (int)meshes.size()) { last_error = "setMeshUv: bad mesh index"; return -1; }
     const IndexRange& vr = meshes[mesh].vertex_indices;
@@ -601,6 +650,9 @@ int Scene::loadConfig(const std::string& path) {
                 } else if (key == "accel") {
                     settings.accel = (val == "bvh") ? ACCEL_BVH : (val == "grid_fast") ? ACCEL_GRID_FAST : ACCEL_GRID;
                     settings.has_accel = true;
+                } else if (key == "direct_light") {
+                    if (val != "0" && val != "1") return fail("bad RENDER line " + b[i]);
+                    settings.direct_light = val == "1";
                 } else if (key.rfind("camera_", 0) == 0) {
                     any_cam = true;
                     const bool vec3 = parse_vec(val, v) && v.size() == 3;

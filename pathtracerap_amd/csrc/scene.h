@@ -50,6 +50,8 @@ struct Grid {                                           // Primitive.h:129-139
     int entity_index = 0;
 };
 
+constexpr int kLightFloats = 20;                        // one record of Scene::lightTable
+
 struct RenderSettings {                                 // Config.h constants, runtime
     int width = 1000, height = 800, iterations = 500, max_bounces = 5;
     int grid[3] = {25, 25, 25};
@@ -59,6 +61,7 @@ struct RenderSettings {                                 // Config.h constants, r
     bool has_camera = false;
     double cam_eye[3] = {0, 0, 0}, cam_target[3] = {0, 0, 0}, cam_up[3] = {0, 1, 0};
     double cam_fov = 45.0, cam_focus = -1.0, cam_lens = 0.0;    // focus < 0: |target - eye|
+    bool direct_light = false;                          // direct_light: 1 (pt_scene_direct_light)
 };
 
 class Scene {
@@ -84,6 +87,14 @@ public:
     // model, read only by a MAT_DIELECTRIC one.  Before or after build, like the smooth flag.
     int setModelIor(int model, float ior);
     float modelIor(int model) const;                    // negative: bad index
+    // The light table of direct lighting (no counterpart in the reference): the triangles of every
+    // EMISSIVE model, models in index order and each model's triangles in mesh order, kLightFloats
+    // floats each, world space: p0, area, e1, the model index (an int's bits), e2, cdf, the unit
+    // normal nl, 0, the emission (the model's colour), 0.  Computed in double, rounded once; cdf is
+    // the running area sum over the total, its last entry 1; a zero-area triangle stays in the
+    // table (nl = 0) and is never chosen.  textured: some EMISSIVE model has a texture bound.
+    // Returns the number of lights.  Before or after build
+    int lightTable(std::vector<float>& recs, double* area_total, bool* textured) const;
     // Albedo textures (no counterpart in the reference, whose Primitive.h declares a uv and never
     // reads it).  Per-vertex uv of one mesh, in addMesh's vertex order; the grid and the BLAS are
     // not touched.  A texture is w x h RGB texels; a model binds one (-1: none; model -1: every
